@@ -17,6 +17,13 @@ C4 KITTI 1241x376 2000 kp, FHD); an RGB-D frame = extract + ComputeStereoFromRGB
 
 Inputs are synthetic (orb_slam_2_ros_amd.synth) and resident in HBM before
 the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run (`--gpus G --steps N --warmup W`) sets up, warms up, times the N
+headline steps and prints the line.  `--full` adds everything else: the
+per-stage launch times and roofline (a profiled pass of its own), the CPU
+baseline, the secondary configurations, C5, the host-fed runs and the per-call
+latencies.  `--dump-outputs DIR` writes what the last timed headline step
+computed (dump_outputs below) so that two builds can be compared.
 """
 from __future__ import annotations
 
@@ -924,14 +931,61 @@ class StubExtractor:
         pass
 
 
+DUMP_STREAMS = 128   # streams of the batch written by --dump-outputs (~21 MB of float32 at 1000 kp)
+DUMP_SEED = 20240
+
+
+def dump_sample(batch: int) -> list:
+    """The local streams --dump-outputs writes: first, last, both sides of the
+    half-batch boundary and a seeded draw, the same for every run of a batch size."""
+    if batch <= DUMP_STREAMS:
+        return list(range(batch))
+    fixed = {0, batch // 2 - 1, batch // 2, batch - 1}
+    rng = np.random.default_rng(DUMP_SEED)
+    rest = [int(b) for b in rng.permutation(batch) if int(b) not in fixed]
+    return sorted(fixed | set(rest[:DUMP_STREAMS - len(fixed)]))
+
+
+def dump_outputs(ex, batch: int, out_dir) -> dict:
+    """Write what the last mono step left for its caller, for the streams of
+    dump_sample(batch), as float32 .npy files in out_dir (rows of all sampled
+    streams one after another, in the order of streams.npy):
+      streams.npy      [S]     the sampled stream slots
+      counts.npy       [S, 3]  keypoints of the frame, keypoints of the previous
+                               frame (the length of its matches row), matches
+      keypoints.npy    [sum, 7]   x, y, size, angle, response, octave, class_id
+      descriptors.npy  [sum, 32]  the descriptor bytes
+      matches.npy      [sum1]     vnMatches12 (index into the frame's keypoints, -1: none)
+    Every value is an integer below 2^24 or a float32 already, so float32 holds it exactly."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    sample = dump_sample(batch)
+    kps, descs, matches, counts = [], [], [], []
+    for b in sample:
+        kp, de = ex.batch_download(b)
+        m12, nm = ex.mono_matches_download(b)
+        kps.append(np.stack([kp[f].astype(np.float32) for f in kp.dtype.names], axis=1).reshape(len(kp), 7))
+        descs.append(np.asarray(de).astype(np.float32).reshape(len(kp), 32))
+        matches.append(np.asarray(m12).astype(np.float32))
+        counts.append((len(kp), len(m12), nm))
+    arrays = {"streams": np.asarray(sample, np.float32), "counts": np.asarray(counts, np.float32).reshape(-1, 3),
+              "keypoints": np.concatenate(kps), "descriptors": np.concatenate(descs),
+              "matches": np.concatenate(matches)}
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {"dir": str(out_dir), "streams": len(sample), "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def run_config(torch, dist, rank, world, dev, w, h, nfeatures, streams, steps, warmup, profile, mode="mono",
-               stub=None, split=2, pipeline=0, kframes=1, overlap=None):
+               stub=None, split=2, pipeline=0, kframes=1, overlap=None, after_timed=None):
     """Times `steps` front-end steps of this rank's `streams` (global stream
     ids: mono / RGB-D frames or stereo pairs, one per stream per step); returns
     (max-over-ranks seconds, stage ms, kps, sanity, frames per launch, extractor).
     kframes (RGB-D only): K consecutive frames of every stream in one launch
     (a step is then K frames per stream; RGB-D frames are independent, the
-    depth lookup reads only the frame's own depth map)."""
+    depth lookup reads only the frame's own depth map).
+    after_timed(ex, batch) is called right after the timed steps, before the
+    profiled pass runs further ones."""
     assert kframes == 1 or mode == "rgbd"
     nstreams = len(streams)
     batch = nstreams * kframes
@@ -981,6 +1035,8 @@ def run_config(torch, dist, rank, world, dev, w, h, nfeatures, streams, steps, w
 
     sync = (lambda: torch.cuda.synchronize(dev)) if on_gpu else (lambda: None)
     el = timed_region(step, steps, max(warmup, 2), sync, dist, world)
+    if after_timed is not None:
+        after_timed(ex, batch)   # (the last timed step's results are still the extractor's current ones)
     stages = None
     if profile and stub is None:
         # per-stage launch durations (HIP events on the launch stream) from a
@@ -1302,10 +1358,15 @@ def main() -> int:
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--nfeatures", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the per-stage profiled pass and roofline, the CPU baseline, the "
+                         "secondary configurations, C5, the host-fed runs and the per-call latencies")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed headline step's outputs (a fixed sample of streams) as DIR/<name>.npy")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary FHD / stereo / RGB-D / C5 configurations")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-profile", action="store_true")
+                    help="with --full: skip the secondary FHD / stereo / RGB-D / C5 configurations")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="with --full: the CPU baseline's budget (0: none)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full or --extra: no per-stage profiled pass")
     ap.add_argument("--extra", default=None,
                     help="time only this EXTRAS config, 'c5' or 'dropin' (diagnostics; prints its dict)")
     ap.add_argument("--stub", action="store_true",
@@ -1333,7 +1394,8 @@ def main() -> int:
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
         dev = torch.device("cuda", local)
         torch.cuda.set_device(dev)
-    profile = not args.no_profile and not args.stub
+    # the profiled pass takes runs of its own: only under --full (and the --extra diagnostics)
+    profile = (args.full or bool(args.extra)) and not args.no_profile and not args.stub
     stub = (lambda w, h: StubExtractor(w, h)) if args.stub else (lambda w, h: None)
     # the stub keeps C5's stream count but not its frame size
     c5_args = (stub(args.width, args.height), args.width, args.height) if args.stub else (None,)
@@ -1372,9 +1434,13 @@ def main() -> int:
 
     w, h, nf, B = args.width, args.height, args.nfeatures, args.batch
     streams = stream_partition(B * world, world, rank)          # weak scaling: B streams per GPU
+    dumped = []
+    dump = None
+    if args.dump_outputs and rank == 0 and not args.stub:   # (rank 0's streams: global ids 0, G, 2 G, ...)
+        dump = lambda ex_, batch_: dumped.append(dump_outputs(ex_, batch_, args.dump_outputs))   # noqa: E731
     el, stages, nkp_last, nm_last, frames_per_launch, ex = run_config(
         torch, dist, rank, world, dev, w, h, nf, streams, args.steps, args.warmup, profile, "mono", stub(w, h),
-        HEADLINE_SPLIT, HEADLINE_PIPE)
+        HEADLINE_SPLIT, HEADLINE_PIPE, after_timed=dump)
     ex.close()
     frames_total = world * B * args.steps
     value = frames_total / el
@@ -1391,7 +1457,7 @@ def main() -> int:
         stub_report = allr
 
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         for key, mode, ew, eh, enf, eb, unit in EXTRAS:
             if args.stub:
                 continue
@@ -1413,9 +1479,11 @@ def main() -> int:
             extras["keyframe_bow_all_gather"] = keyframe_exchange(torch, dist, world, dev)
 
     if rank == 0:
-        sizes = level_geometry(w, h, nf) if not args.stub else [(w, h)]
-        roof, stage_ms = roofline_block(sizes, nkp_last, stages, frames_per_launch, value / world, "mono")
-        run_cpu = world == 1 and args.cpu_seconds > 0 and not args.stub
+        roof = stage_ms = None
+        if stages:
+            roof, stage_ms = roofline_block(level_geometry(w, h, nf), nkp_last, stages, frames_per_launch,
+                                            value / world, "mono")
+        run_cpu = args.full and world == 1 and args.cpu_seconds > 0 and not args.stub
         cpu = cpu_baseline(w, h, nf, args.cpu_seconds) if run_cpu else None
         if cpu is not None:
             # the host's share of cores, all at once: the CPUs this process may
@@ -1427,7 +1495,7 @@ def main() -> int:
             cpu["all_cores"] = cpu_baseline_threads(w, h, nf, max(2.0, args.cpu_seconds / 2), nthr)
             cpu["all_cores"]["threads_from"] = {"affinity_cpus": aff, "OMP_NUM_THREADS": omp or None}
             # the timing build stays selected: every CPU time in extras uses it too
-        full = world == 1 and not args.no_extras and not args.stub
+        full = args.full and world == 1 and not args.no_extras and not args.stub
         matchers = matcher_latencies() if full else None
         if full:
             # one rank's share of C5 at 8 GPUs (8 streams), one frame per stream
@@ -1449,6 +1517,7 @@ def main() -> int:
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -1466,6 +1535,8 @@ def main() -> int:
             "extras": extras,
             "matchers_per_call": matchers,
         }
+        if dumped:
+            line["dumped_outputs"] = dumped[0]
         if stub_report is not None:
             line["stub"] = stub_report
         print(json.dumps(line), flush=True)

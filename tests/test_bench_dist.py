@@ -121,7 +121,7 @@ def test_bench_launcher_two_ranks_stub():
     B, steps, warmup, w, h = 6, 3, 1, 64, 48
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--stub", "--width", str(w),
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--stub", "--full", "--width", str(w),
                         "--height", str(h), "--batch", str(B), "--steps", str(steps), "--warmup", str(warmup),
                         "--cpu-seconds", "0"], capture_output=True, text=True, timeout=300, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-2000:]
@@ -143,6 +143,37 @@ def test_bench_launcher_two_ranks_stub():
     c5 = line["extras"]["c5_rgbd_fhd_64_streams"]
     assert c5["streams_total"] == 64 and c5["streams_per_gpu"] == 32
     assert c5["keyframe_all_gather"]["ranks"] == 2
+
+
+def test_plain_run_measures_only_the_headline():
+    """Without --full the line carries the headline (value, ms_per_step over
+    exactly --steps timed steps) and none of the secondary measurements."""
+    import json
+    import subprocess
+    steps, warmup = 4, 3
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--stub", "--width", "64", "--height",
+                        "48", "--batch", "6", "--steps", str(steps), "--warmup", str(warmup)],
+                       capture_output=True, text=True, timeout=120, cwd=str(ROOT))
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["full"] is False and line["steps"] == steps and line["warmup"] == warmup
+    assert line["stub"][0]["calls"] == warmup + steps
+    assert line["ms_per_step"] > 0 and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(6 * 1e3 / line["ms_per_step"], rel=0.05)
+    assert line["extras"] == {} and line["cpu_baseline"] is None and line["matchers_per_call"] is None
+    assert line["roofline"] is None and line["stage_ms_per_step"] is None
+
+
+def test_dump_sample_is_fixed():
+    """--dump-outputs writes the same streams on every run of a batch size:
+    all of a small batch; 128 of a large one, the ends and the half-batch
+    boundary among them."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    assert bench.dump_sample(8) == list(range(8))
+    s = bench.dump_sample(3072)
+    assert s == bench.dump_sample(3072) and s == sorted(set(s)) and len(s) == bench.DUMP_STREAMS
+    assert {0, 1535, 1536, 3071} <= set(s) and all(0 <= b < 3072 for b in s)
 
 
 def test_bench_rejects_world_mismatch():

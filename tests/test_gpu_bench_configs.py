@@ -395,6 +395,39 @@ def test_sharding_changes_no_stream(mode, w, h, nf, total, world):
     assert len({v[0] for v in whole.values()}) == min(total, bench.UNIQUE_SCENES)
 
 
+def test_dump_outputs_holds_the_last_step(tmp_path):
+    """bench.dump_outputs (bench.py --dump-outputs) writes, in float32 and
+    without loss, exactly what the last mono step left: every sampled stream's
+    keypoints, descriptors and matches, in the order of streams.npy."""
+    import torch
+    w, h, B = 640, 480, 5
+    _, _, fr, _ = _frames(torch, "mono", w, h, list(range(B)))
+    ex = ORBextractor(1000, 1.2, 8, 20, 7)
+    ex.reserve(w, h, B)
+    for t in range(2):
+        ex.mono_step_device(fr[t].data_ptr(), w * h, w, B, 100, 0.9, True)
+    torch.cuda.synchronize()
+    info = bench.dump_outputs(ex, B, tmp_path / "out")
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert sorted(got) == ["counts", "descriptors", "keypoints", "matches", "streams"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert info["streams"] == B and info["bytes"] == sum(a.nbytes for a in got.values())
+    assert got["streams"].tolist() == list(range(B))
+    k0 = m0 = 0
+    for b in range(B):
+        kp, de = ex.batch_download(b)
+        m12, nm = ex.mono_matches_download(b)
+        assert got["counts"][b].tolist() == [len(kp), len(m12), nm] and len(kp) > 0 and nm > 0
+        rows = got["keypoints"][k0:k0 + len(kp)]
+        for j, f in enumerate(kp.dtype.names):
+            assert np.array_equal(rows[:, j].astype(kp.dtype[f]), kp[f]), f"stream {b} {f}"
+        assert np.array_equal(got["descriptors"][k0:k0 + len(kp)].astype(np.uint8), de), f"stream {b}"
+        assert np.array_equal(got["matches"][m0:m0 + len(m12)].astype(np.int32), m12), f"stream {b}"
+        k0, m0 = k0 + len(kp), m0 + len(m12)
+    assert k0 == len(got["keypoints"]) == len(got["descriptors"]) and m0 == len(got["matches"])
+    ex.close()
+
+
 def test_pack_device_equals_download():
     """orbx_batch_pack_device (the keyframe exchange's send buffer, config C5)
     holds exactly what orbx_batch_download returns for every stream: counts,

@@ -24,5 +24,6 @@ summ ${TAG}_fhd gpurun_out/traffic_fhd_$TAG.json 192 "FHD 1920x1080 mono B=192 u
 timeout -k 10 400 bash tools/profile.sh ${TAG}_fhd_stereo --extra stereo_fhd_1920x1080 || exit 1
 summ ${TAG}_fhd_stereo gpurun_out/traffic_fhd_stereo_$TAG.json 384 \
     "FHD 1920x1080 stereo, 192 pairs = 384 frames a launch, unsplit ($TAG)" || exit 1
-timeout -k 10 600 python bench.py > gpurun_out/bench_$TAG.log 2>&1 || { tail -5 gpurun_out/bench_$TAG.log; exit 1; }
-tail -c 400 gpurun_out/bench_$TAG.log
+BENCH_LOG=${BENCH_LOG:-bench_$TAG.log}
+timeout -k 10 600 python bench.py --full > "$BENCH_LOG" 2>&1 || { tail -5 "$BENCH_LOG"; exit 1; }
+tail -c 400 "$BENCH_LOG"
