@@ -46,7 +46,11 @@ int orbx_device_count(void);
  * reference counterpart): "bow_repairs" -- in the last orbx_search_by_bow(_batch)
  * call, the A features whose two best B features (of a node of <= 64 B
  * features) included one an earlier A feature had taken, so that the exact
- * in-order pass over the untaken ones ran.  ORBX_EINVAL for an unknown name. */
+ * in-order pass over the untaken ones ran.  "ba_cmap_oob" -- in the last
+ * orbx_local_ba_fast or orbx_ba_debug_step_fast call, the entries of the
+ * camera x point map outside [-1, ne) that the dense Schur product skipped,
+ * over all its solves (0 unless the map is stale).  ORBX_EINVAL for an
+ * unknown name. */
 int orbx_debug_counter(const char *name, int64_t *value);
 
 /* ---- ORB_SLAM2::ORBextractor ------------------------------------------ */
@@ -605,6 +609,14 @@ int orbx_local_ba_fast(int device, const float *Tcw, const uint8_t *fixed, int n
 int orbx_ba_debug_step(int device, const float *Tcw, const uint8_t *fixed, int ncam, const float *Xw, int npt,
                        const orbx_ba_edge *edges, int ne, int robust, double lambda, double *x_out,
                        double *chi2_out, int *solved);
+/* The same step as a trial of orbx_local_ba_fast solves it: the dense Schur
+ * product, its Cholesky (the global-memory one above its size limit) and the
+ * dense back-substitution.  orbx_debug_counter("ba_cmap_oob") then holds the
+ * camera x point map entries the product skipped as out of range (0 unless
+ * the map is stale); it is set by orbx_local_ba_fast too.  Test hook. */
+int orbx_ba_debug_step_fast(int device, const float *Tcw, const uint8_t *fixed, int ncam, const float *Xw, int npt,
+                            const orbx_ba_edge *edges, int ne, int robust, double lambda, double *x_out,
+                            double *chi2_out, int *solved);
 
 /* Device evaluation of the restated sincosf / fastAtan2 (test hook). */
 int orbx_debug_trig(int device, const float *angles, float *s, float *c, int n,

@@ -1951,12 +1951,22 @@ struct OBA {
                             const int pa = E[cl[i1][a]].point, pb = E[cl[i2][b]].point;
                             if (pa < pb) { ++a; continue; }
                             if (pb < pa) { ++b; continue; }
-                            double s = 0;
-                            for (int k = 0; k < 3; ++k)
-                                s = s + bdinv[18 * (size_t)cl[i1][a] + 3 * r + k] * hpl_e[18 * (size_t)cl[i2][b] + 3 * c + k];
-                            acc = acc - s;
-                            ++a;
-                            ++b;
+                            // a camera that observes the point more than once adds its
+                            // edges into one Hpl block in g2o: every edge of i1 at this
+                            // point meets every edge of i2 at it
+                            size_t a2 = a, b2 = b;
+                            while (a2 < cl[i1].size() && E[cl[i1][a2]].point == pa) ++a2;
+                            while (b2 < cl[i2].size() && E[cl[i2][b2]].point == pa) ++b2;
+                            for (size_t ia = a; ia < a2; ++ia)
+                                for (size_t ib = b; ib < b2; ++ib) {
+                                    double s = 0;
+                                    for (int k = 0; k < 3; ++k)
+                                        s = s + bdinv[18 * (size_t)cl[i1][ia] + 3 * r + k] *
+                                                    hpl_e[18 * (size_t)cl[i2][ib] + 3 * c + k];
+                                    acc = acc - s;
+                                }
+                            a = a2;
+                            b = b2;
                         }
                         S[(size_t)(6 * i1 + r) * n + 6 * i2 + c] = acc;
                         S[(size_t)(6 * i2 + c) * n + 6 * i1 + r] = acc;

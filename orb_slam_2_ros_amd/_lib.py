@@ -149,6 +149,7 @@ _SIGNATURES = {
     "orbx_local_ba": (I32, [I32, P, P, I32, P, I32, P, I32, I32, I32, P, P, P, P]),
     "orbx_local_ba_fast": (I32, [I32, P, P, I32, P, I32, P, I32, I32, I32, P, P, P, P]),
     "orbx_ba_debug_step": (I32, [I32, P, P, I32, P, I32, P, I32, I32, ctypes.c_double, P, P, P]),
+    "orbx_ba_debug_step_fast": (I32, [I32, P, P, I32, P, I32, P, I32, I32, ctypes.c_double, P, P, P]),
 }
 
 # orbx_covis_fn

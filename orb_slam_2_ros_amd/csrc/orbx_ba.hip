@@ -445,12 +445,20 @@ __global__ void k_ba_pairs(const int2 *pairs, int npairs, const int32_t *coffs, 
         const int pa = epoint[clist[a]], pb = epoint[clist[b]];
         if (pa < pb) { ++a; continue; }
         if (pb < pa) { ++b; continue; }
-        const int e1 = clist[a], e2 = clist[b];
-        double s = 0;
-        for (int k = 0; k < 3; ++k) s = s + bdinv[18 * (int64_t)e1 + 3 * r + k] * eo[e2].hpl[3 * c + k];
-        acc = acc - s;
-        ++a;
-        ++b;
+        // (a camera observing the point more than once: its edges share one
+        // Hpl block in g2o, so every edge of i1 here meets every edge of i2)
+        int a2 = a, b2 = b;
+        while (a2 < ae && epoint[clist[a2]] == pa) ++a2;
+        while (b2 < be && epoint[clist[b2]] == pa) ++b2;
+        for (int ia = a; ia < a2; ++ia)
+            for (int ib = b; ib < b2; ++ib) {
+                const int e1 = clist[ia], e2 = clist[ib];
+                double s = 0;
+                for (int k = 0; k < 3; ++k) s = s + bdinv[18 * (int64_t)e1 + 3 * r + k] * eo[e2].hpl[3 * c + k];
+                acc = acc - s;
+            }
+        a = a2;
+        b = b2;
     }
     const int n = 6 * nf;
     S[(int64_t)(6 * i1 + r) * n + 6 * i2 + c] = acc;
@@ -735,7 +743,7 @@ typedef double orbx_f64x4 __attribute__((ext_vector_type(4)));
 // the per-edge B D^-1 products; equal to rounding.
 constexpr int kSchurKC = 512;
 __global__ void k_ba_schur_ops(int npt, int nf, int CT, int ucol, int kp, const int32_t *cmap, const EdgeOut *eo,
-                               int ne, const double *lu, double *M) {
+                               int ne, const double *lu, double *M, unsigned *oob) {
     const int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (idx >= (int64_t)kp * CT) return;
     const int k = (int)(idx / CT), col = (int)(idx - (int64_t)k * CT);
@@ -751,6 +759,8 @@ __global__ void k_ba_schur_ops(int npt, int nf, int CT, int ucol, int kp, const 
                 v = kk == 0 ? l[0] * h[0]
                   : kk == 1 ? fma(l[2], h[1], l[1] * h[0])
                             : fma(l[5], h[2], fma(l[4], h[1], l[3] * h[0]));
+            } else if (ed != -1 && kk == 0 && r == 0) {   // (a stale or torn map entry, once: "ba_cmap_oob")
+                atomicAdd(oob, 1u);
             }
         } else if (col == ucol) {
             v = l[6 + kk];
@@ -1787,6 +1797,8 @@ bool dense_schur_on() {
     return on;
 }
 
+thread_local int64_t g_cmap_oob = 0;   // orbx::ba_cmap_oob_last
+
 class BA {
 public:
     BA(Graph &g, BAWs &ws) : g_(g), st_(ws.st), ws_(ws) {}
@@ -1878,6 +1890,8 @@ public:
     double *d_fpart = nullptr;                     // its per-workgroup partials
     double *d_epart = nullptr;                     // k_ba_errors_sums' per-workgroup partials (2 each)
     unsigned *d_fcount = nullptr;                  // its finished-workgroup counter (zeroed by alloc, reset by the last)
+    // d_fcount[2]: map entries k_ba_schur_ops skipped as out of range, summed over the call
+    int read_cmap_oob();
     uint8_t *h_stage = nullptr;                // set_active's uploads: flags, then h_coffs_ | clist
     int32_t *h_coffs_ = nullptr;
     size_t schur_bytes() {   // (fast mode) sizes the dense Schur product's buffers
@@ -2284,7 +2298,7 @@ int BA::solve_async(double lambda) {
     if (dn) {   // S and bs from one dense product (k_ba_schur_*)
         const int64_t tot = (int64_t)schur_kp_ * schur_ct_;
         hipLaunchKernelGGL(k_ba_schur_ops, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st_, g.npt, g.nf,
-                           schur_ct_, schur_ucol_, schur_kp_, d_cmap, d_eo, g.ne, d_lu, d_M);
+                           schur_ct_, schur_ucol_, schur_kp_, d_cmap, d_eo, g.ne, d_lu, d_M, d_fcount + 2);
         hipLaunchKernelGGL(k_ba_schur_mfma, dim3(schur_nblk_, schur_nch_), dim3(256), 0, st_, d_M, schur_ct_,
                            schur_h_, d_spart);
         hipLaunchKernelGGL(k_ba_schur_sum, dim3((n * n + n + 255) / 256), dim3(256), 0, st_, d_spart, schur_nch_,
@@ -2351,6 +2365,15 @@ int BA::solve_async(double lambda) {
                            terms, flag, d_x + n);
     }
     return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EIO;
+}
+
+int BA::read_cmap_oob() {   // (fast mode; synchronises the stream)
+    unsigned v = 0;
+    if (fast_ && (hipMemcpyAsync(&v, d_fcount + 2, 4, hipMemcpyDeviceToHost, st_) != hipSuccess ||
+                  hipStreamSynchronize(st_) != hipSuccess))
+        return ORBX_EIO;
+    g_cmap_oob = v;
+    return ORBX_OK;
 }
 
 int BA::update_gated() {   // (the trial's backup of the estimate is written by the update itself)
@@ -2450,12 +2473,15 @@ int BA::download(double *pts, std::vector<double> &chi2, std::vector<uint8_t> &f
                                   g_.ne, d_active, 0, 1, d_err, d_chi2, d_rho, d_front, nullptr, nullptr);
     chi2.resize(std::max(g_.ne, 1));
     front.resize(std::max(g_.ne, 1));
-    if (hipMemcpyAsync(g_.poses.data(), d_pose, sizeof(Pose) * g_.ncam, hipMemcpyDeviceToHost, st_) != hipSuccess ||
+    unsigned oob = 0;   // (fast mode: "ba_cmap_oob", with the same synchronisation)
+    if ((fast_ && hipMemcpyAsync(&oob, d_fcount + 2, 4, hipMemcpyDeviceToHost, st_) != hipSuccess) ||
+        hipMemcpyAsync(g_.poses.data(), d_pose, sizeof(Pose) * g_.ncam, hipMemcpyDeviceToHost, st_) != hipSuccess ||
         (g_.npt && hipMemcpyAsync(pts, d_pts, 24 * (size_t)g_.npt, hipMemcpyDeviceToHost, st_) != hipSuccess) ||
         (g_.ne && hipMemcpyAsync(chi2.data(), d_chi2, 8 * (size_t)g_.ne, hipMemcpyDeviceToHost, st_) != hipSuccess) ||
         (g_.ne && hipMemcpyAsync(front.data(), d_front, g_.ne, hipMemcpyDeviceToHost, st_) != hipSuccess) ||
         hipStreamSynchronize(st_) != hipSuccess)
         return ORBX_EIO;
+    g_cmap_oob = oob;
     return ORBX_OK;
 }
 
@@ -2596,6 +2622,7 @@ static int local_ba(int device, bool fast, const float *Tcw, const uint8_t *fixe
     if (ncam < 0 || npt < 0 || ne < 0 || iters1 < 0 || iters2 < 0 || (ncam && (!Tcw || !fixed || !Tcw_out)) ||
         (npt && (!Xw || !Xw_out)) || (ne && (!edges || !outlier)))
         return ORBX_EINVAL;
+    g_cmap_oob = 0;
     // ORBX_BA_TIMING: host-side phase times of this call on stderr (diagnostics)
     static const bool timing = std::getenv("ORBX_BA_TIMING") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
@@ -2696,9 +2723,10 @@ int orbx_local_ba_fast(int device, const float *Tcw, const uint8_t *fixed, int n
 // One linear system of the first pass: computeActiveErrors, buildSystem,
 // setLambda(lambda), solve -- the step x (poses, then points) and the robust
 // chi2, without the update (test hook for the oracle's identical step).
-int orbx_ba_debug_step(int device, const float *Tcw, const uint8_t *fixed, int ncam, const float *Xw, int npt,
-                       const orbx_ba_edge *edges, int ne, int robust, double lambda, double *x_out, double *chi2_out,
-                       int *solved) {
+static int debug_step(int device, bool fast, const float *Tcw, const uint8_t *fixed, int ncam, const float *Xw,
+                      int npt, const orbx_ba_edge *edges, int ne, int robust, double lambda, double *x_out,
+                      double *chi2_out, int *solved) {
+    g_cmap_oob = 0;
     if (ncam < 0 || npt < 0 || ne < 0 || !x_out || !chi2_out || !solved || (ncam && (!Tcw || !fixed)) ||
         (npt && !Xw) || (ne && !edges))
         return ORBX_EINVAL;
@@ -2714,16 +2742,32 @@ int orbx_ba_debug_step(int device, const float *Tcw, const uint8_t *fixed, int n
     for (size_t i = 0; i < 3 * (size_t)npt; ++i) pts[i] = Xw[i];
     {
         BA ba(g, ws);
+        ba.fast_ = fast;   // (a fast trial's linear solve: dense Schur product, its Cholesky and back-substitution)
         std::vector<uint8_t> act(std::max(ne, 1), 1);
         if (!(rc = ba.alloc()) && !(rc = ba.upload(pts.data()))) {
             ba.set_active(act);
             if (!(rc = ba.errors(robust != 0, chi2_out)) && !(rc = ba.build()) && !(rc = ba.solve(lambda, solved))) {
                 const size_t m = 6 * (size_t)g.nf + 3 * (size_t)npt;
                 if (m && (hipMemcpy(x_out, ba.d_x, 8 * m, hipMemcpyDeviceToHost) != hipSuccess)) rc = ORBX_EIO;
+                if (!rc) rc = ba.read_cmap_oob();
             }
         }
     }
     return rc;
 }
 
+int orbx_ba_debug_step(int device, const float *Tcw, const uint8_t *fixed, int ncam, const float *Xw, int npt,
+                       const orbx_ba_edge *edges, int ne, int robust, double lambda, double *x_out, double *chi2_out,
+                       int *solved) {
+    return debug_step(device, false, Tcw, fixed, ncam, Xw, npt, edges, ne, robust, lambda, x_out, chi2_out, solved);
+}
+
+int orbx_ba_debug_step_fast(int device, const float *Tcw, const uint8_t *fixed, int ncam, const float *Xw, int npt,
+                            const orbx_ba_edge *edges, int ne, int robust, double lambda, double *x_out,
+                            double *chi2_out, int *solved) {
+    return debug_step(device, true, Tcw, fixed, ncam, Xw, npt, edges, ne, robust, lambda, x_out, chi2_out, solved);
+}
+
 }  // extern "C"
+
+int64_t orbx::ba_cmap_oob_last() { return g_cmap_oob; }

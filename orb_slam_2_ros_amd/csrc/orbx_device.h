@@ -270,5 +270,8 @@ bool resize_window_fits(const Plan &hp);
 bool plan_resize_waves(Plan &hp);   // fills hp.rw, or leaves it empty (block kernel)
 bool plan_pyr_regions(Plan &hp);   // fills hp.rgn, or leaves rgn_n = 0
 bool use_pyr_regions(const Plan &hp, int B);
+// orbx_debug_counter "ba_cmap_oob" (orbx_ba.hip): entries of the camera x point
+// map outside [-1, ne) that the calling thread's last fast-mode BA call skipped
+int64_t ba_cmap_oob_last();
 
 }  // namespace orbx

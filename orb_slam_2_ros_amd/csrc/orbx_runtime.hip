@@ -2299,6 +2299,7 @@ int orbx_search_by_bow_batch(int device, int variant, orbx_bow_problem *problems
 int orbx_debug_counter(const char *name, int64_t *value) {
     if (!name || !value) return ORBX_EINVAL;
     if (!std::strcmp(name, "bow_repairs")) { *value = g_debug.bow_repairs; return ORBX_OK; }
+    if (!std::strcmp(name, "ba_cmap_oob")) { *value = orbx::ba_cmap_oob_last(); return ORBX_OK; }
     return ORBX_EINVAL;
 }
 

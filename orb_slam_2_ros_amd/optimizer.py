@@ -32,8 +32,10 @@ def local_bundle_adjustment(Tcw, fixed, Xw, edges, iters=(5, 10), device: int = 
     return To, Xo, out[:len(E)].astype(bool), (int(its[0]), int(its[1]))
 
 
-def debug_step(Tcw, fixed, Xw, edges, robust=True, lam=1e-3, device: int = 0):
-    """One LM linear system of the first pass (test hook): (x, chi2, solved)."""
+def debug_step(Tcw, fixed, Xw, edges, robust=True, lam=1e-3, device: int = 0, fast: bool = False):
+    """One LM linear system of the first pass (test hook): (x, chi2, solved).
+    fast: orbx_ba_debug_step_fast, the step as an orbx_local_ba_fast trial
+    solves it."""
     T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 3, 4)
     F = np.ascontiguousarray(fixed, np.uint8)
     X = np.ascontiguousarray(Xw, np.float32).reshape(-1, 3)
@@ -42,6 +44,7 @@ def debug_step(Tcw, fixed, Xw, edges, robust=True, lam=1e-3, device: int = 0):
     x = np.zeros(max(n, 1), np.float64)
     chi2 = ctypes.c_double(0)
     ok = ctypes.c_int(0)
-    check(load().orbx_ba_debug_step(device, ptr(T), ptr(F), len(T), ptr(X), len(X), ptr(E), len(E), int(robust),
-                                    float(lam), ptr(x), ctypes.byref(chi2), ctypes.byref(ok)), "orbx_ba_debug_step")
+    fn = load().orbx_ba_debug_step_fast if fast else load().orbx_ba_debug_step
+    check(fn(device, ptr(T), ptr(F), len(T), ptr(X), len(X), ptr(E), len(E), int(robust), float(lam), ptr(x),
+             ctypes.byref(chi2), ctypes.byref(ok)), "orbx_ba_debug_step")
     return x[:n], chi2.value, bool(ok.value)

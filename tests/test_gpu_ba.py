@@ -8,6 +8,7 @@ device's sin/cos, so an ulp there could in principle show)."""
 import numpy as np
 import pytest
 
+from orb_slam_2_ros_amd._lib import debug_counter
 from orb_slam_2_ros_amd.optimizer import debug_step, local_bundle_adjustment
 from orb_slam_2_ros_amd.synth_ba import make_ba_problem
 
@@ -65,7 +66,12 @@ def test_local_ba_workspace_reuse(oracle_mod):
     """The per-device workspace across calls: problems that grow, shrink and
     cross the LDS / global-memory Cholesky boundary (21 and 22 free
     keyframes: 126 / 132 unknowns) in turn, a repeated observation in
-    between; every call identical to the oracle."""
+    between; every call identical to the oracle.  The repeated observation
+    (call 3) is on a free camera, so it reaches the Schur complement: there
+    the oracle and the merge walk give the camera's two edges one Hpl block,
+    as g2o does (tests/test_ba_reference.py holds the oracle to the dense
+    reference on such a graph).  Their earlier one-to-one pairing gave other
+    values here, four float ulps away in the last pose."""
     seq = [(22, 2000, 31), (5, 400, 32), (21, 1800, 33), (6, 600, 9), (22, 2000, 34), (21, 1800, 33)]
     for k, (n_local, n_points, seed) in enumerate(seq):
         P = make_ba_problem(n_local=n_local, n_fixed=3, n_points=n_points, seed=seed)
@@ -98,6 +104,8 @@ def test_local_ba_fast_mode_within_tolerance(seed, n_local, n_points, oracle_mod
 
 def _fast_close(P, e, oracle_mod, tag):
     Tg, Xg, og, ig = local_bundle_adjustment(P["Tcw"], P["fixed"], P["Xw"], e, fast=True)
+    # (no entry of the camera x point map outside [-1, ne) was skipped by the dense Schur product)
+    assert debug_counter("ba_cmap_oob") == 0, (tag, debug_counter("ba_cmap_oob"))
     To, Xo, oo, io = oracle_mod.local_ba(P["Tcw"], P["fixed"], P["Xw"], e)
     assert np.array_equal(og, oo), (tag, np.nonzero(og != oo)[0][:8])
     assert np.abs(Tg - To).max() <= 1e-4 * max(1.0, np.abs(To).max()), (tag, np.abs(Tg - To).max())
@@ -135,5 +143,6 @@ def test_local_ba_fast_mode_mono_only_and_empty(oracle_mod):
     _fast_close(P, P["edges"], oracle_mod, "mono")
     e = P["edges"][:0]
     Tg, Xg, og, ig = local_bundle_adjustment(P["Tcw"], P["fixed"], P["Xw"], e, fast=True)
+    assert debug_counter("ba_cmap_oob") == 0
     assert len(og) == 0
     assert np.abs(Tg - P["Tcw"]).max() <= 1e-6 and np.abs(Xg - P["Xw"]).max() <= 1e-6 * np.abs(P["Xw"]).max()
