@@ -30,10 +30,6 @@ constexpr int kHist = 30;
 constexpr int kThLow = 50;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr int kRepairs = kHist + 1;   // count slot of the repair passes (after the match count)
-#ifndef ORBX_BOW_LANES_A
-#define ORBX_BOW_LANES_A 1   // nodes of <= 64 B features: lanes take A's features (0: one A feature at a time)
-#endif
-constexpr bool kBowLanesA = ORBX_BOW_LANES_A;
 
 __device__ inline int hamming_rr(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1) {
     return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
@@ -126,8 +122,8 @@ __device__ __attribute__((always_inline)) void bow_match_node(const BowBufs &a, 
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const float *F = a.tri;
-    if (nbk <= 64 && kBowLanesA) {
-        // The lanes take A's features (64 at a time) and B's features are
+    if (nbk <= 64) {
+        // Nodes of <= 64 B features: the lanes take A's features (64 at a time) and B's features are
         // broadcast one at a time from the registers above: every A feature's
         // two best keys over all of B, with no cross-lane reduction per
         // feature.  SearchByBoW's greedy pass then walks the features in

@@ -99,10 +99,7 @@ struct LevelGeom {
 // at the 1.2 scale factor the source rows advance by 6 every 5 output rows,
 // so every lane group starts at the same phase and the lanes of a wave reuse
 // the previous row's horizontal pass together (resize_tile).
-#ifndef ORBX_RS_K
-#define ORBX_RS_K 10
-#endif
-constexpr int kResizeK = ORBX_RS_K;
+constexpr int kResizeK = 10;
 struct ResizeWave {
     double sx = 0, sy = 0;     // source / destination size ratio, as make_resize_taps
     int twg = 64, twg_shift = 6;

@@ -165,16 +165,6 @@ struct orbx_extractor {
     int split = 1;   // orbx_extractor_split / ORBX_SPLIT=2 turn it on
     hipStream_t part_stream[kMaxParts] = {};
     hipEvent_t fork_ev = nullptr, done_ev[kMaxParts] = {};
-    // Stagger (ORBX_STAGGER=s, s in 1..3): part 1 starts after part 0's first
-    // s stages (resize, FAST, quadtree), so the parts' latency-bound kernels
-    // meet the other part's VALU-bound ones instead of each other.
-    int stagger = 0;
-    hipEvent_t stag_ev = nullptr;
-    // Serial chunks (ORBX_CHUNKS=c, diagnostic): an unsplit batch runs as c
-    // chunks one after another on the launch stream, each chunk's resize,
-    // FAST, quadtree and describe back to back, so a chunk's pyramid is still
-    // in the 256 MB MALL when its describe re-reads it.
-    int chunks = 1;
 
     // Matcher overlap (orbx_extractor_overlap_match, default off): a mono
     // step's SearchForInitialization runs on match_stream, which the launch
@@ -212,7 +202,6 @@ struct orbx_extractor {
         for (auto &ps : part_stream)
             if (ps) (void)hipStreamDestroy(ps);
         if (fork_ev) (void)hipEventDestroy(fork_ev);
-        if (stag_ev) (void)hipEventDestroy(stag_ev);
         if (match_stream) (void)hipStreamDestroy(match_stream);
         if (ext_ev) (void)hipEventDestroy(ext_ev);
         if (match_ev) (void)hipEventDestroy(match_ev);
@@ -520,22 +509,7 @@ struct Parts {
 };
 
 // A stream for the extractor's own forks (batch parts, level pipeline).
-// ORBX_QUEUES=dedicated: one made by hipExtStreamCreateWithCUMask (every CU),
-// which the runtime gives a hardware queue of its own, so two forks never
-// share one of the process's pooled queues (GPU_MAX_HW_QUEUES) and serialise.
-hipError_t fork_stream(hipStream_t *s) {
-    static const bool dedicated = [] {
-        const char *q = std::getenv("ORBX_QUEUES");
-        return q && std::strcmp(q, "dedicated") == 0;
-    }();
-    if (!dedicated) return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-        return hipErrorInvalidValue;
-    std::vector<uint32_t> mask((ncu + 31) / 32, 0xFFFFFFFFu);
-    return hipExtStreamCreateWithCUMask(s, (uint32_t)mask.size(), mask.data());
-}
+hipError_t fork_stream(hipStream_t *s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
 
 // Splits `batch` into sub-batches on the part streams (forked from st), or a
 // single part on st itself.
@@ -725,21 +699,6 @@ int run_extract(orbx_extractor *ex, int si, const uint8_t *d_images, int64_t str
     FrameBufs pf[orbx_extractor::kMaxParts];
     for (int k = 0; k < P.n; ++k) pf[k] = offset_frames(ex, fb, P.b0[k]);
     const hipStream_t m = P.s[0];
-    if (ex->chunks > 1 && P.n == 1 && !ex->pipeline) {
-        mark(ex, 0, m);   // (one span for the whole extraction, no per-stage times)
-        const int nc = std::min(ex->chunks, batch);
-        for (int k = 0; k < nc; ++k) {
-            const int c0 = batch * k / nc, cn = batch * (k + 1) / nc - c0;
-            const FrameBufs fc = offset_frames(ex, fb, c0);
-            if (launch_resize(ex->dp, ex->plan, fc, cn, m) != hipSuccess ||
-                launch_fast(ex->dp, ex->plan, fc, cn, m) != hipSuccess ||
-                launch_quadtree(ex->dp, fc, cn, m) != hipSuccess || !gate_describe(ex, m) ||
-                launch_describe(ex->dp, fc, cn, m) != hipSuccess)
-                return ORBX_EIO;
-        }
-        for (int i = 1; i <= kStageMatch; ++i) mark(ex, i, m);
-        return ORBX_OK;   // (no stage marks: stage times come from unchunked runs)
-    }
     if (ex->pipeline && make_pipe(ex)) {
         for (int k = 0; k < P.n; ++k) {
             // (the deep form needs the per-level resize kernels: not the
@@ -750,27 +709,6 @@ int run_extract(orbx_extractor *ex, int si, const uint8_t *d_images, int64_t str
             if (rc) return rc;
         }
         return ORBX_OK;
-    }
-    auto stage = [&](int k, int st) -> bool {
-        switch (st) {
-            case 0: return launch_resize(ex->dp, ex->plan, pf[k], P.nb[k], P.s[k]) == hipSuccess;
-            case 1: return launch_fast(ex->dp, ex->plan, pf[k], P.nb[k], P.s[k]) == hipSuccess;
-            case 2: return launch_quadtree(ex->dp, pf[k], P.nb[k], P.s[k]) == hipSuccess;
-            default: return gate_describe(ex, P.s[k]) && launch_describe(ex->dp, pf[k], P.nb[k], P.s[k]) == hipSuccess;
-        }
-    };
-    if (P.n == 2 && ex->stagger > 0 &&
-        (ex->stag_ev || hipEventCreateWithFlags(&ex->stag_ev, hipEventDisableTiming) == hipSuccess)) {
-        const int sg = std::min(ex->stagger, 3);
-        for (int st = 0; st < 4; ++st) {
-            if (!stage(0, st)) return ORBX_EIO;
-            if (st == sg - 1 && (hipEventRecord(ex->stag_ev, P.s[0]) != hipSuccess ||
-                                 hipStreamWaitEvent(P.s[1], ex->stag_ev, 0) != hipSuccess))
-                return ORBX_EIO;
-        }
-        for (int st = 0; st < 4; ++st)
-            if (!stage(1, st)) return ORBX_EIO;
-        return ORBX_OK;   // (no stage marks: stage times come from unsplit runs)
     }
     mark(ex, 0, m);
     for (int k = 0; k < P.n; ++k)
@@ -952,8 +890,6 @@ orbx_extractor *orbx_extractor_create(int device, int nfeatures, float scaleFact
     if (const char *pe = std::getenv("ORBX_PIPE_EARLY")) ex->pipe_early = std::max(1, std::atoi(pe));
     if (const char *pd = std::getenv("ORBX_PIPE_DESC")) ex->pipe_desc = std::atoi(pd) != 0;
     if (const char *om = std::getenv("ORBX_OVERLAP_MATCH")) ex->overlap_match = std::atoi(om) != 0;
-    if (const char *sg = std::getenv("ORBX_STAGGER")) ex->stagger = std::max(0, std::min(std::atoi(sg), 3));
-    if (const char *ck = std::getenv("ORBX_CHUNKS")) ex->chunks = std::max(1, std::min(std::atoi(ck), 64));
     // geometry tables for the getters are size independent; plan a nominal size
     ex->plan = make_plan(640, 480, nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST);
     return ex;

@@ -183,10 +183,7 @@ __device__ int band_sort(const StereoBufs &a, int b, const Bands &d, int *ws, in
     return *s_span;
 }
 
-#ifndef ORBX_STEREO_WALK
-#define ORBX_STEREO_WALK 4
-#endif
-constexpr int kWalk = ORBX_STEREO_WALK;   // band positions per batch of descriptor loads
+constexpr int kWalk = 4;   // band positions per batch of descriptor loads
 
 // SCR: the pair's bands sorted once by k_band_sort into its scratch (read
 // from L2), instead of every block sorting them into its LDS.

@@ -4,7 +4,8 @@ half-rate VALU opcodes (profiles/r02_valu_ops.txt), SGPR-operand VALU (half
 rate whatever the opcode), LDS and VMEM instructions.  Static counts: a loop
 body counts once.
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off --cuda-device-only -S \\
-          [-DORBX_PHASE_PROF] -o /tmp/x.s orb_slam_2_ros_amd/csrc/orbx_extract.hip
+          [-DORBX_PHASE_PROF] -o /tmp/x.s orb_slam_2_ros_amd/csrc/orbx_fast.hip
+    (the kernel's stage file: orbx_pyramid / orbx_fast / orbx_quadtree / orbx_describe .hip)
     python tools/isa_mix.py /tmp/x.s k_fastILb0 [--ops]"""
 import re
 import sys
