@@ -190,16 +190,27 @@ constexpr int kColS = 44;                   // column-major row-pass buffer: str
 // row buffer overlays it (kDescRowOff = 0; 3.5 KB a wave instead of 5.5:
 // LDS no longer caps the occupancy).
 constexpr int kDescWaves = 8;    // waves per SIMD the launch bounds ask for (VGPR budget 512 / this)
+// Waves (consecutive keypoint slots of a frame) per workgroup.  The waves share
+// nothing, so the width only sets how many wave slots and how much LDS are
+// taken and given back at once: one-wave workgroups measured fastest
+// (k_describe per 3072 VGA frames: 2.40 ms with four waves and their
+// orientations on wave 0, 2.30 with four and 2.20 with one wave each
+// evaluating its own; profiles/r07_ab_describe.txt)
+constexpr int kDescW = 1;
+constexpr int kDescThreads = 64 * kDescW;
 constexpr int kDescRowOff = 0;   // the row buffer's offset in the wave's LDS: over the patch
 constexpr int kDescWaveLds = std::max(kDescRowOff + kRowCols * kColS * 2 + 8,    // (+ 8: the row pass's spill, below)
                                       47 * kDescPS + 64);                         // 3528 B
 static_assert((kDescR - 3 + kBlurR) + 7 < kColS, "a sample's 16-byte read stays in its column");
 constexpr int kDescWaveStride = (kDescWaveLds + 15) & ~15;
 static_assert(47 * kDescPS + 63 < kDescWaveLds, "MFMA row-pass reads stay inside the wave's LDS");
-// LDS is allocated per workgroup in 512-byte granules: 4 waves + 48 B of
-// shared angle records must fit kDescWaves workgroups in a CU's 160 KB
-static_assert(kDescWaves * ((4 * kDescWaveStride + 48 + 511) & ~511) <= 160 * 1024,
+// A CU holds 4 kDescWaves = 32 waves, that is 32 / kDescW workgroups.  LDS is
+// allocated per workgroup in 512-byte granules (3584 B for the one wave's 3536):
+// that many workgroups must fit a CU's 160 KB (32 x 3584 B = 112 KB)
+static_assert((4 * kDescWaves) % kDescW == 0 && kDescThreads <= 1024, "whole workgroups fill the CU's wave slots");
+static_assert(4 * kDescWaves / kDescW * ((kDescW * kDescWaveStride + 511) & ~511) <= 160 * 1024,
               "k_describe: LDS for the occupancy the launch bounds ask");
+static_assert(kDescW * kDescWaveStride <= 64 * 1024, "static LDS of one workgroup");
 
 // The row pass as an int8 matrix product (v_mfma_i32_16x16x32_i8): outputs
 // j = 0..15 of a 16-column tile from the tile's 32 input columns,
@@ -267,17 +278,15 @@ __device__ inline void stage_desc_patch(uint8_t *dst, const uint8_t *img, int pi
 }
 
 template <bool PIPE>
-__global__ __launch_bounds__(kThreads, kDescWaves) void k_describe(DevPlan p, FrameBufs fb, int s0, int ns, int write_total,
+__global__ __launch_bounds__(kDescThreads, kDescWaves) void k_describe(DevPlan p, FrameBufs fb, int s0, int ns, int write_total,
                                                                    uint32_t gmagic) {
-    __shared__ __align__(16) uint8_t lds[4 * kDescWaveStride];
-    __shared__ int s_mom[4][2];      // each wave's (m01, m10)
-    __shared__ float s_ang[4][3];    // each wave's (angle, sin, cos), computed by wave 0
+    __shared__ __align__(16) uint8_t lds[kDescW * kDescWaveStride];
     PHASE_START();
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
     int bx, b;
     xcd_block_2d(bx, b, gmagic);
-    const int slot = s0 + bx * 4 + wave;
-    const bool in_range = slot < p.out_cap && bx * 4 + wave < ns;
+    const int slot = s0 + bx * kDescW + wave;
+    const bool in_range = slot < p.out_cap && bx * kDescW + wave < ns;
     // level of this slot (plan table) and the selected key: scalar loads
     const int l = in_range ? (int)p.slot_level[slot] : 0;
     // (32-bit index: the plan bounds max_batch * out_cap below 2^31, orbx_runtime.hip)
@@ -316,7 +325,6 @@ __global__ __launch_bounds__(kThreads, kDescWaves) void k_describe(DevPlan p, Fr
     const int cl = __builtin_amdgcn_readlane(cq, l);
     const int off = __builtin_amdgcn_readlane((int)scan, l) - cl;
     if (write_total && bx == 0 && tid == 0) fb.nkps[b] = __builtin_amdgcn_readlane((int)scan, kMaxLevels - 1);
-    // (no early exit: every wave reaches the block's two barriers)
     const LevelArgs g = p.la[l];
     const int i = slot - g.out_off;
     const bool valid = in_range && i < cl;
@@ -329,7 +337,10 @@ __global__ __launch_bounds__(kThreads, kDescWaves) void k_describe(DevPlan p, Fr
     // column-pass taps as u16 pairs for v_dot2_u32_u16 over rows (r, r+1), (r+2, r+3), (r+4, r+5), (r+6, r+7)
     constexpr u16x2 kK01 = {(unsigned short)k0, (unsigned short)k1}, kK23 = {(unsigned short)k2, (unsigned short)k3},
                     kK21 = {(unsigned short)k2, (unsigned short)k1}, kK0z = {(unsigned short)k0, 0};
-    if (valid) {
+    // (the waves of a workgroup share nothing: no barrier to reach)
+    if (!valid) return;
+    int m01 = 0, m10 = 0;   // IC_Angle's moments, wave-uniform
+    {
 
     // 1. stage the 43x43 unblurred neighbourhood at patch columns 2..44: dword
     //    loads when it lies inside the level, else byte loads with reflect-101
@@ -409,10 +420,8 @@ __global__ __launch_bounds__(kThreads, kDescWaves) void k_describe(DevPlan p, Fr
                 "v_add_u32_dpp %1, %1, %1 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
                 "s_nop 1"
                 : "+v"(y), "+v"(x));
-            if (lane == 0) {
-                s_mom[wave][0] = __builtin_amdgcn_readlane(y, 63);
-                s_mom[wave][1] = __builtin_amdgcn_readlane(x, 63);
-            }
+            m01 = __builtin_amdgcn_readlane(y, 63);
+            m10 = __builtin_amdgcn_readlane(x, 63);
         }
         PHASE_MARK(1, 1);   // moments
         // row pass: nine 16 x 16 output tiles (rows 16 rt.., patch columns
@@ -453,22 +462,17 @@ __global__ __launch_bounds__(kThreads, kDescWaves) void k_describe(DevPlan p, Fr
     }
     PHASE_MARK(1, 2);   // row pass
     }   // kStopDesc
-    }   // valid
-    // The orientation (fastAtan2) and its sincosf are wave-uniform scalar
-    // chains of ~90 VALU each: wave 0 evaluates the block's four at once (lane
-    // = wave), instead of every wave issuing the chain for one value.
-    __syncthreads();
-    if (wave == 0 && lane < 4) {
-        const float a = fast_atan2_deg((float)s_mom[lane][0], (float)s_mom[lane][1]);
-        float sa, ca;
-        glibc_sincosf(__fmul_rn(a, (float)(3.14159265358979323846 / 180.f)), &sa, &ca);
-        s_ang[lane][0] = a;
-        s_ang[lane][1] = sa;
-        s_ang[lane][2] = ca;
     }
-    __syncthreads();
-    if (!valid) return;
-    const float angle = s_ang[wave][0], sa = s_ang[wave][1], ca = s_ang[wave][2];
+    // The orientation (fastAtan2) and its sincosf: wave-uniform chains of ~90
+    // VALU that every wave issues for its own keypoint.  One wave evaluating its
+    // workgroup's orientations between two barriers issued a quarter of that
+    // per keypoint and measured slower: the chain advances one instruction per
+    // turn of its SIMD's waves, and the workgroup's other waves waited it out
+    // (profiles/r07_ab_describe.txt).
+    const float angle = fast_atan2_deg((float)m01, (float)m10);
+    float sa, ca;
+    glibc_sincosf(__fmul_rn(angle, (float)(3.14159265358979323846 / 180.f)), &sa, &ca);
+    PHASE_MARK(1, 5);   // orientation
     const int64_t kp_index = (int64_t)b * p.max_kps + off + i;
     // the keypoint record (the matchers downstream index their grids with it)
     auto write_record = [&]() {
@@ -619,8 +623,8 @@ hipError_t launch_blur(const DevPlan &p, const FrameBufs &fb, int B, hipStream_t
 }
 
 hipError_t launch_describe(const DevPlan &p, const FrameBufs &fb, int B, hipStream_t st) {
-    const uint32_t gx = (p.out_cap + 3) / 4;
-    hipLaunchKernelGGL(k_describe<false>, dim3(gx, B), dim3(kThreads), 0, st, p, fb, 0, p.out_cap, 1,
+    const uint32_t gx = (p.out_cap + kDescW - 1) / kDescW;
+    hipLaunchKernelGGL(k_describe<false>, dim3(gx, B), dim3(kDescThreads), 0, st, p, fb, 0, p.out_cap, 1,
                        grid_magic(gx, B));
     return hipGetLastError();
 }
@@ -630,8 +634,8 @@ hipError_t launch_describe(const DevPlan &p, const FrameBufs &fb, int B, hipStre
 hipError_t launch_describe_level(const DevPlan &p, const Plan &hp, const FrameBufs &fb, int B, hipStream_t st, int l,
                                  int l_end) {
     const int s0 = hp.lv[l].out_off, ns = hp.lv[l_end - 1].out_off + hp.lv[l_end - 1].out_cap - s0;
-    const uint32_t gx = (ns + 3) / 4;
-    hipLaunchKernelGGL(k_describe<true>, dim3(gx, B), dim3(kThreads), 0, st, p, fb, s0, ns,
+    const uint32_t gx = (ns + kDescW - 1) / kDescW;
+    hipLaunchKernelGGL(k_describe<true>, dim3(gx, B), dim3(kDescThreads), 0, st, p, fb, s0, ns,
                        l_end == hp.nlevels ? 1 : 0, grid_magic(gx, B));
     return hipGetLastError();
 }

@@ -41,8 +41,8 @@ torch.cuda.synchronize()
 fn(buf.ctypes.data, 24, 1)
 names = {0: ["prologue+stage", "ini: zero+compass+compact", "ini: arc scores", "ini: NMS+out",
              "min: zero+compass+compact", "min: arc scores", "min: NMS+out", "-"],
-         1: ["prologue+stage", "moments+atan", "row pass", "sincos+offsets+column pass", "round+ballot+write",
-             "-", "-", "-"],
+         1: ["prologue+stage", "moments", "row pass", "offsets+column pass", "round+ballot+write",
+             "orientation (atan+sincos)", "-", "-"],
          2: ["gather", "roots", "full: child counts", "full: scan+children", "final: child counts",
              "final: sort", "final: splits", "output"]}
 for k, kname in ((0, "k_fast"), (1, "k_describe"), (2, "k_quadtree")):
