@@ -37,6 +37,7 @@ _SIG = {
     "orbo_pyramid": (SZ, [P, I32, I32, SZ, F32, I32, P]),
     "orbo_level_candidates": (I32, [P, I32, I32, I32, I32, P, I32]),
     "orbo_level_candidates_cells": (I32, [P, I32, I32, I32, I32, P, I32, P, I32, P]),
+    "orbo_level_cells": (I32, [I32, I32, P, I32]),
     "orbo_distribute": (I32, [P, I32, I32, I32, I32, P]),
     "orbo_extract": (I32, [P, I32, I32, SZ, I32, F32, I32, I32, I32, P, P, I32, P]),
     "orbo_search_for_initialization": (I32, [P, P, I32, P, P, I32, I32, I32, P, P, I32, F32, I32]),
@@ -170,6 +171,15 @@ def level_candidates_cells(lvl: np.ndarray, ini=20, mn=7):
                                           len(cells), ctypes.byref(nc))
     assert n >= 0
     return out[:3 * n].reshape(n, 3), cells[:nc.value].copy()
+
+
+def level_cells(w: int, h: int) -> np.ndarray:
+    """The (x0, y0, x1, y1) windows FAST runs on for a w x h level, in cell
+    order; a window's evaluated interior is 3 px inside it."""
+    out = np.zeros((20000, 4), np.int32)   # 135 x 135 cells at 4095 x 4095
+    n = lib().orbo_level_cells(int(w), int(h), _p(out), len(out))
+    assert n >= 0
+    return out[:n].copy()
 
 
 def distribute(cands: np.ndarray, w: int, h: int, N: int) -> np.ndarray:

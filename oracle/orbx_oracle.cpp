@@ -342,10 +342,12 @@ Geometry make_geometry(int W, int H, int nfeatures, float scaleFactorF, int nlev
 // ---------------------------------------------------------------------------
 // Cell loop of ComputeKeyPointsOctTree (ORBextractor.cc:796-863).
 // ---------------------------------------------------------------------------
-void level_candidates(const uint8_t *lvl, int w, int h, size_t step, int iniTh, int minTh,
-                      std::vector<Corner> &cands, std::vector<int> *cell_counts = nullptr) {
-    cands.clear();
-    if (cell_counts) cell_counts->clear();
+// The sub-images cv::FAST is called on, [x0, x1) x [y0, y1) in level pixels,
+// in the reference's visiting order (skipped cells left out).
+struct CellWin { int x0, y0, x1, y1; };
+
+void level_cells(int w, int h, std::vector<CellWin> &cells) {
+    cells.clear();
     const float W = 30;
     const int minBX = 19 - 3, minBY = minBX;
     const int maxBX = w - 19 + 3, maxBY = h - 19 + 3;
@@ -353,7 +355,6 @@ void level_candidates(const uint8_t *lvl, int w, int h, size_t step, int iniTh, 
     const int nCols = (int)(width / W), nRows = (int)(height / W);
     if (nCols <= 0 || nRows <= 0) return;
     const int wCell = (int)std::ceil(width / nCols), hCell = (int)std::ceil(height / nRows);
-    std::vector<Corner> cell;
     for (int i = 0; i < nRows; ++i) {
         const float iniY = (float)(minBY + i * hCell);
         float maxY = iniY + hCell + 6;
@@ -364,14 +365,26 @@ void level_candidates(const uint8_t *lvl, int w, int h, size_t step, int iniTh, 
             float maxX = iniX + wCell + 6;
             if (iniX >= maxBX - 6) continue;
             if (maxX > maxBX) maxX = (float)maxBX;
-            const int y0 = (int)iniY, x0 = (int)iniX;
-            const uint8_t *sub = lvl + (size_t)y0 * step + x0;
-            const int sw = (int)maxX - x0, sh = (int)maxY - y0;
-            fast9(sub, sw, sh, step, iniTh, cell);
-            if (cell.empty()) fast9(sub, sw, sh, step, minTh, cell);
-            for (const Corner &c : cell) cands.push_back({c.x + x0, c.y + y0, c.score});
-            if (cell_counts) cell_counts->push_back((int)cell.size());
+            cells.push_back({(int)iniX, (int)iniY, (int)maxX, (int)maxY});
         }
+    }
+}
+
+void level_candidates(const uint8_t *lvl, int w, int h, size_t step, int iniTh, int minTh,
+                      std::vector<Corner> &cands, std::vector<int> *cell_counts = nullptr) {
+    cands.clear();
+    if (cell_counts) cell_counts->clear();
+    std::vector<CellWin> cells;
+    level_cells(w, h, cells);
+    std::vector<Corner> cell;
+    for (const CellWin &cw : cells) {
+        const int x0 = cw.x0, y0 = cw.y0;
+        const uint8_t *sub = lvl + (size_t)y0 * step + x0;
+        const int sw = cw.x1 - x0, sh = cw.y1 - y0;
+        fast9(sub, sw, sh, step, iniTh, cell);
+        if (cell.empty()) fast9(sub, sw, sh, step, minTh, cell);
+        for (const Corner &c : cell) cands.push_back({c.x + x0, c.y + y0, c.score});
+        if (cell_counts) cell_counts->push_back((int)cell.size());
     }
 }
 
@@ -699,6 +712,20 @@ int orbo_level_candidates_cells(const uint8_t *lvl, int w, int h, int iniTh, int
         xys[3 * i] = c[i].x; xys[3 * i + 1] = c[i].y; xys[3 * i + 2] = c[i].score;
     }
     for (size_t i = 0; i < cc.size(); ++i) cell_counts[i] = cc[i];
+    return n;
+}
+
+// The FAST sub-image windows (x0, y0, x1, y1) of a w x h level, in the same
+// cell order.  Returns the cell count, or -(count) if cap is too small.
+int orbo_level_cells(int w, int h, int32_t *rects, int cap) {
+    std::vector<CellWin> cells;
+    level_cells(w, h, cells);
+    const int n = (int)cells.size();
+    if (n > cap) return -n;
+    for (int i = 0; i < n; ++i) {
+        rects[4 * i] = cells[i].x0; rects[4 * i + 1] = cells[i].y0;
+        rects[4 * i + 2] = cells[i].x1; rects[4 * i + 3] = cells[i].y1;
+    }
     return n;
 }
 

@@ -66,6 +66,10 @@ int   orbo_level_candidates(const uint8_t *lvl, int w, int h, int iniTh, int min
  * tools/tie_heap replays the per-cell vector<KeyPoint> allocations). */
 int   orbo_level_candidates_cells(const uint8_t *lvl, int w, int h, int iniTh, int minTh,
                                   int32_t *xys, int cap, int32_t *cell_counts, int cell_cap, int *ncells);
+/* The sub-image windows (x0, y0, x1, y1; x1 / y1 exclusive) that cell loop
+ * hands to cv::FAST for a w x h level, in the same cell order (test inputs
+ * are placed by them).  Returns the cell count (or -needed if > cap). */
+int   orbo_level_cells(int w, int h, int32_t *rects, int cap);
 /* DistributeOctTree on a candidate list (ORBextractor.cc:561-787): writes the
  * selected candidate indices in output order; returns the count. */
 void  orbo_tie_stats(int64_t out[9], int reset);   /* diagnostic, see orbx_oracle.cpp */

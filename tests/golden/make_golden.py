@@ -5,6 +5,11 @@ These are REGRESSION fixtures of this project's CPU restatement (oracle/),
 not reference-produced vectors: the reference has none and cannot be built
 here (parity unpinned).  They freeze the oracle's behaviour so
 any later change to it -- or to the GPU path -- is caught without re-deriving.
+Every stage of the extractor, the sampling table and the assembly of
+operator() are also held to the independent restatement in tests/pyref.py
+(tests/test_oracle_kat.py); what stays unpinned is only the arithmetic at the
+OpenCV boundary (resize, blur, FAST, fastAtan2, cvRound), restated from the
+published 3.2 algorithms and not compared with an OpenCV build.
 Inputs are regenerated from (w, h, seed) by orb_slam_2_ros_amd.synth; the
 input's SHA-256 is stored to detect generator drift.
 """

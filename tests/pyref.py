@@ -331,6 +331,197 @@ def round_half_away(v) -> int:
     return int(math.floor(v + 0.5)) if v >= 0 else -int(math.floor(-v + 0.5))
 
 
+# ---- ORBextractor: tables, IC_Angle, computeOrbDescriptor, operator() --------
+# Written from the reference's text (ORBextractor.cc:77-147, 416-479, 790-892,
+# 1083-1185) and DESIGN.md §3.5.  fastAtan2 and glibc sincosf are the oracle's
+# exported scalars: both are pinned by their own known-answer tests
+# (test_fast_atan2_axes_and_accuracy, test_sincosf_is_glibc) and by the device
+# comparison of every float in [0, 2 pi], so restating their
+# polynomials a third time here would pin nothing new.
+KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
+                           ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
+UMAX = [15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3]
+
+
+def _oracle_scalars():
+    from oracle import oracle
+    return oracle.fast_atan2, oracle.sincosf
+
+
+def orb_pattern():
+    """The 512 (x, y) sample points of orb_pattern.inc (the table both the
+    oracle and k_describe include), as an int array (512, 2)."""
+    import re
+    from pathlib import Path
+    text = (Path(__file__).resolve().parents[1] / "orb_slam_2_ros_amd" / "csrc" / "orb_pattern.inc").read_text()
+    body = text[text.rindex("ORBX_PATTERN_BEGIN") + len("ORBX_PATTERN_BEGIN"):text.rindex("ORBX_PATTERN_END")]
+    vals = [int(v) for v in re.findall(r"-?\d+", body)]
+    assert len(vals) == 1024
+    return np.array(vals, np.int64).reshape(512, 2)
+
+
+def umax_table() -> list:
+    """ORBextractor.cc:463-478 (HALF_PATCH_SIZE 15)."""
+    hp = 15
+    half_diag = f32(f32(hp) * f32(math.sqrt(f32(2.0)))) / f32(2)      # sqrt(2.f) is float
+    vmax, vmin = cv_floor(f32(half_diag + f32(1))), int(math.ceil(float(half_diag)))
+    um = [0] * (hp + 1)
+    for v in range(vmax + 1):
+        um[v] = cv_round(math.sqrt(float(hp * hp) - v * v))
+    v0 = 0
+    for v in range(hp, vmin - 1, -1):
+        while um[v0] == um[v0 + 1]:
+            v0 += 1
+        um[v] = v0
+        v0 += 1
+    return um
+
+
+def extractor_tables(w, h, nfeatures, scale, nlevels):
+    """(mvScaleFactor, mnFeaturesPerLevel, level sizes): ORBextractor.cc:422-455
+    with scaleFactor the double member of ORBextractor.h, and :1157-1159."""
+    sfd = float(f32(scale))
+    sf = [f32(1.0)]
+    for _ in range(1, nlevels):
+        sf.append(f32(float(sf[-1]) * sfd))
+    inv = [f32(f32(1.0) / s) for s in sf]
+    factor = f32(1.0 / sfd)
+    nd = f32(f32(f32(nfeatures) * f32(f32(1) - factor)) / f32(f32(1) - f32(float(factor) ** float(nlevels))))
+    quota, total = [], 0
+    for _ in range(nlevels - 1):
+        quota.append(cv_round(nd))
+        total += quota[-1]
+        nd = f32(nd * factor)
+    quota.append(max(nfeatures - total, 0))
+    sizes = [(cv_round(f32(f32(w) * s)), cv_round(f32(f32(h) * s))) for s in inv]
+    return sf, quota, sizes
+
+
+def fast_cells(w, h) -> list:
+    """The (iniX, iniY, maxX, maxY) windows of ORBextractor.cc:796-837."""
+    min_bx = min_by = 19 - 3
+    max_bx, max_by = w - 19 + 3, h - 19 + 3
+    width, height = f32(max_bx - min_bx), f32(max_by - min_by)
+    ncols, nrows = int(width / f32(30)), int(height / f32(30))
+    if ncols <= 0 or nrows <= 0:
+        return []
+    wcell, hcell = int(math.ceil(width / f32(ncols))), int(math.ceil(height / f32(nrows)))
+    out = []
+    for i in range(nrows):
+        ini_y = min_by + i * hcell
+        max_y = ini_y + hcell + 6
+        if ini_y >= max_by - 3:
+            continue
+        max_y = min(max_y, max_by)
+        for j in range(ncols):
+            ini_x = min_bx + j * wcell
+            max_x = ini_x + wcell + 6
+            if ini_x >= max_bx - 6:
+                continue
+            out.append((ini_x, ini_y, min(max_x, max_bx), max_y))
+    return out
+
+
+def ic_moments(lvl: np.ndarray, x: int, y: int, umax=UMAX):
+    """(m_01, m_10) of IC_Angle (ORBextractor.cc:77-101): integer sums over the
+    umax disc of the unblurred level."""
+    img = lvl.astype(np.int64)
+    m01 = m10 = 0
+    for u in range(-15, 16):
+        m10 += u * int(img[y, x + u])
+    for v in range(1, 16):
+        vsum, d = 0, umax[v]
+        for u in range(-d, d + 1):
+            plus, minus = int(img[y + v, x + u]), int(img[y - v, x + u])
+            vsum += plus - minus
+            m10 += u * (plus + minus)
+        m01 += v * vsum
+    return m01, m10
+
+
+def ic_angle(lvl: np.ndarray, x: int, y: int, umax=UMAX) -> np.float32:
+    fast_atan2, _ = _oracle_scalars()
+    m01, m10 = ic_moments(lvl, x, y, umax)
+    return f32(fast_atan2(float(f32(m01)), float(f32(m10))))
+
+
+def orb_sample_offsets(angle_deg, pattern):
+    """(row, col) offsets of the 512 samples (GET_VALUE, ORBextractor.cc:118-120):
+    float32 products and sums, each rounded on its own, then cvRound."""
+    _, sincosf = _oracle_scalars()
+    factor_pi = f32(math.pi / float(f32(180.0)))
+    angle = f32(f32(angle_deg) * factor_pi)
+    b, a = sincosf(float(angle))
+    a, b = f32(a), f32(b)
+    px, py = pattern[:, 0].astype(np.float32), pattern[:, 1].astype(np.float32)
+    rows = np.rint(np.add(np.multiply(px, b, dtype=np.float32), np.multiply(py, a, dtype=np.float32),
+                          dtype=np.float32)).astype(np.int64)
+    cols = np.rint(np.subtract(np.multiply(px, a, dtype=np.float32), np.multiply(py, b, dtype=np.float32),
+                               dtype=np.float32)).astype(np.int64)
+    return rows, cols
+
+
+def orb_samples(blur: np.ndarray, x: int, y: int, angle_deg, pattern) -> np.ndarray:
+    rows, cols = orb_sample_offsets(angle_deg, pattern)
+    return blur[y + rows, x + cols].astype(np.int64)
+
+
+def orb_descriptor(blur: np.ndarray, x: int, y: int, angle_deg, pattern) -> np.ndarray:
+    """computeOrbDescriptor (ORBextractor.cc:108-147) on the blurred level:
+    bit k of byte i is sample(16 i + 2 k) < sample(16 i + 2 k + 1), strictly."""
+    s = orb_samples(blur, x, y, angle_deg, pattern)
+    desc = np.zeros(32, np.uint8)
+    for i in range(32):
+        val = 0
+        for k in range(8):
+            t0, t1 = s[16 * i + 2 * k], s[16 * i + 2 * k + 1]
+            val |= int(t0 < t1) << k
+        desc[i] = val
+    return desc
+
+
+def extract(img: np.ndarray, nfeatures=1000, scale=1.2, nlevels=8, ini=20, mn=7):
+    """ORBextractor::operator() (ORBextractor.cc:1083-1149) over ComputePyramid
+    (:1152-1185) and ComputeKeyPointsOctTree (:790-892), composed of this
+    file's stages.  Returns (keypoints, descriptors, per-level details)."""
+    h, w = img.shape
+    sf, quota, sizes = extractor_tables(w, h, nfeatures, scale, nlevels)
+    umax, pattern = umax_table(), orb_pattern()
+    pyr = [np.ascontiguousarray(img)]
+    for l in range(1, nlevels):
+        pyr.append(resize_linear(pyr[l - 1], sizes[l][0], sizes[l][1]))       # from level l - 1 (:1171)
+    per_level = []
+    for l in range(nlevels):
+        lw, lh = sizes[l]
+        cands = []
+        for (x0, y0, x1, y1) in fast_cells(lw, lh):
+            sub = pyr[l][y0:y1, x0:x1]
+            cell = fast_cell(sub, ini)
+            if not cell:
+                cell = fast_cell(sub, mn)
+            cands += [(x + x0, y + y0, s) for (x, y, s) in cell]               # (:856-857, :881-882)
+        keys = [cands[i] for i in distribute(cands, lw, lh, quota[l])]
+        angles = [ic_angle(pyr[l], x, y, umax) for (x, y, _) in keys]         # unblurred level (:891)
+        per_level.append((keys, angles))
+    n = sum(len(k) for k, _ in per_level)
+    kps = np.zeros(n, KEYPOINT_DTYPE)
+    desc = np.zeros((n, 32), np.uint8)
+    o = 0
+    for l, (keys, angles) in enumerate(per_level):
+        if not keys:
+            continue
+        blur = gauss7(pyr[l])                                                  # a borderless clone (:1129-1130)
+        size = f32(int(f32(f32(31) * sf[l])))                                  # scaledPatchSize is an int (:874)
+        for (x, y, s), ang in zip(keys, angles):
+            desc[o] = orb_descriptor(blur, x, y, ang, pattern)
+            px, py = f32(x), f32(y)
+            if l != 0:
+                px, py = f32(px * sf[l]), f32(py * sf[l])                      # (:1139-1145)
+            kps[o] = (px, py, size, ang, f32(s), l, -1)
+            o += 1
+    return kps, desc, per_level
+
+
 # ---- Frame::ComputeStereoMatches (Frame.cc:502-676) --------------------------
 def compute_stereo_matches(pyr_l, pyr_r, scale, inv_scale, kl, dl, kr, dr, mbf, mb):
     """Straight transcription of the reference loop (vRowIndices as lists,

@@ -512,3 +512,83 @@ def test_local_ba_step_solves_the_normal_equations(oracle_mod):
         b[cols] += -w * J.T @ r0
     xr = np.linalg.solve(H + lam * np.eye(n), b)
     assert np.allclose(x, xr, rtol=2e-3, atol=2e-5 * np.abs(xr).max())
+
+
+# ---- orientation, descriptor and operator() against pyref --------------------
+# The sampling table is shared by the oracle and k_describe (orb_pattern.inc):
+# SHA-256 of its 512 (x, y) pairs as int8 bytes, recorded once from the
+# reference's bit_pattern_31_ parsed the way tools/gen_pattern.py does.
+ORB_PATTERN_SHA256 = "2164181aea6ff9ac426ca512d5130d15e1f6e3cd47b1cbdd568bbe1e55d49023"
+
+
+def test_orb_pattern_digest():
+    import hashlib
+    pat = pyref.orb_pattern()
+    assert pat.shape == (512, 2) and np.abs(pat).max() <= 13
+    assert hashlib.sha256(pat.astype(np.int8).tobytes()).hexdigest() == ORB_PATTERN_SHA256
+
+
+def test_umax_table():
+    assert pyref.umax_table() == [15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3] == pyref.UMAX
+
+
+def test_level_tables_and_cells_vs_python(oracle_mod):
+    for w, h, nf, scale, nlev in [(640, 480, 1000, 1.2, 8), (752, 480, 1200, 1.2, 8), (152, 100, 500, 1.2, 4),
+                                  (160, 120, 300, 2.0, 3), (333, 250, 777, 1.1, 10), (91, 62, 50, 1.5, 2)]:
+        lw, lh, q, s = oracle_mod.levels(w, h, nf, scale, nlev)
+        sf, quota, sizes = pyref.extractor_tables(w, h, nf, scale, nlev)
+        assert np.array_equal(np.array(sf, np.float32), s) and quota == q.tolist()
+        assert sizes == list(zip(lw.tolist(), lh.tolist()))
+        for l in range(nlev):
+            assert pyref.fast_cells(*sizes[l]) == [tuple(r) for r in oracle_mod.level_cells(*sizes[l]).tolist()]
+
+
+def _extract_vs_python(oracle_mod, img, nf, scale, nlev, ini, mn, min_kps):
+    ko, do = oracle_mod.extract(img, nf, scale, nlev, ini, mn)
+    kp, dp, _ = pyref.extract(img, nf, scale, nlev, ini, mn)
+    assert len(ko) == len(kp) and len(ko) >= min_kps
+    for f in ko.dtype.names:
+        assert np.array_equal(ko[f], kp[f]), f"keypoint field {f}: first difference at {np.nonzero(ko[f] != kp[f])[0][:1]}"
+    assert ko.tobytes() == kp.astype(ko.dtype).tobytes()
+    assert np.array_equal(do, dp), f"descriptor rows {np.nonzero((do != dp).any(1))[0][:5]}"
+    return ko
+
+
+def test_extract_vs_python_synth(oracle_mod):
+    """operator() end to end: the default 8 levels at 1.2 on a 160 x 120 synth frame."""
+    k = _extract_vs_python(oracle_mod, synth.frame(160, 120, 15), 300, 1.2, 8, 20, 7, 100)
+    assert len(set(k["octave"].tolist())) >= 3
+
+
+@pytest.mark.parametrize("name,ini,mn,scale,nlev,min_kps", [
+    ("uniform", 20, 7, 1.2, 4, 400),      # every level at its quota: the quadtree's final phase
+    ("dots", 20, 7, 1.2, 1, 36),          # one level; zero moments and descriptors of ties
+    ("binary", 128, 127, 2.0, 3, 90),     # scale 2.0; samples of 0 / 255 only
+    ("plateau", 7, 20, 1.2, 4, 200),      # iniTh < minTh; the lattice cell
+])
+def test_extract_vs_python_adversarial(name, ini, mn, scale, nlev, min_kps, oracle_mod):
+    import extract_cases as ec
+    _extract_vs_python(oracle_mod, ec.image(name, ini, mn), ec.NFEATURES, scale, nlev, ini, mn, min_kps)
+
+
+def test_ic_angle_and_descriptor_known_answers(oracle_mod):
+    """Hand-derived: a lone bright pixel has zero moments (fastAtan2(0, 0) = 0);
+    a second one 5 px to the right / below gives 0 / 90 degrees exactly; on a
+    flat patch every pair ties and the strict '<' leaves the descriptor 0; on
+    a left-to-right ramp at angle 0 bit j is x[2j] < x[2j + 1] of the table."""
+    img = np.zeros((60, 60), np.uint8)
+    img[30, 30] = 255
+    assert pyref.ic_moments(img, 30, 30) == (0, 0) and pyref.ic_angle(img, 30, 30) == 0.0
+    img[30, 35] = 255
+    assert pyref.ic_moments(img, 30, 30) == (0, 5 * 255) and pyref.ic_angle(img, 30, 30) == 0.0
+    img[30, 35] = 0
+    img[35, 30] = 255
+    assert pyref.ic_moments(img, 30, 30) == (5 * 255, 0) and pyref.ic_angle(img, 30, 30) == 90.0
+    pat = pyref.orb_pattern()
+    assert not pyref.orb_descriptor(np.full((60, 60), 77, np.uint8), 30, 30, 123.0, pat).any()
+    ramp = np.tile(np.arange(60, dtype=np.uint8) * 4, (60, 1))
+    want = np.packbits((pat[0::2, 0] < pat[1::2, 0]).astype(np.uint8), bitorder="little")
+    assert np.array_equal(pyref.orb_descriptor(ramp, 30, 30, 0.0, pat), want)
+    # at 90 degrees (a = cos ~ -4e-8, b = 1) the sample row is x and the column -y
+    want90 = np.packbits((-pat[0::2, 1] < -pat[1::2, 1]).astype(np.uint8), bitorder="little")
+    assert np.array_equal(pyref.orb_descriptor(ramp, 30, 30, 90.0, pat), want90)
