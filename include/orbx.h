@@ -618,6 +618,59 @@ int orbx_ba_debug_step_fast(int device, const float *Tcw, const uint8_t *fixed, 
                             const orbx_ba_edge *edges, int ne, int robust, double lambda, double *x_out,
                             double *chi2_out, int *solved);
 
+/* ---- Optimizer::PoseOptimization (Optimizer.cc:265-509) --------------------
+ * The motion-only optimisation of one frame: a single free SE3 vertex, one
+ * EdgeSE3ProjectXYZOnlyPose (monocular) or EdgeStereoSE3ProjectXYZOnlyPose
+ * per feature that has a map point, four rounds of at most ten Levenberg-
+ * Marquardt iterations with the inlier / outlier classification between them.
+ * The whole optimisation of a problem is one wave of one kernel launch
+ * (k_pose_optimize); DESIGN.md §3.13 is the numeric specification. */
+typedef struct orbx_pose_obs {
+    float Xw[3];       /* pMP->GetWorldPos() */
+    float u, v;        /* mvKeysUn[i].pt */
+    float ur;          /* mvuRight[i]; < 0: monocular observation */
+    float inv_sigma2;  /* mvInvLevelSigma2[octave] */
+} orbx_pose_obs;
+
+typedef struct orbx_pose_camera {
+    float fx, fy, cx, cy, bf; /* the frame's intrinsics (bf: stereo only) */
+} orbx_pose_camera;
+
+/* One frame.  Tcw: row-major 3x4 float (mTcw); obs: the n features that have
+ * a map point, in feature order.  Tcw_out: the pose SetPose receives (a byte
+ * copy of Tcw when n < 3, where the reference returns before SetPose);
+ * outlier[n]: mvbOutlier of those features; chi2[n] (nullable): each
+ * observation's last computed chi2; *n_inliers: the return value;
+ * iterations[4] (nullable): LM iterations run per round.  Host arrays,
+ * synchronous. */
+int orbx_pose_optimization(int device, const float *Tcw, const orbx_pose_camera *cam, const orbx_pose_obs *obs, int n,
+                           float *Tcw_out, uint8_t *outlier, double *chi2, int *n_inliers, int *iterations);
+/* nproblems frames at once: Tcw[nproblems][12], cams[nproblems], problem p's
+ * observations obs[offsets[p] .. offsets[p + 1]) (offsets[0] = 0, ascending);
+ * outlier / chi2 (nullable) in the same layout, n_inliers[nproblems],
+ * iterations[nproblems][4] (nullable).  One upload, one launch, one
+ * download; synchronous. */
+int orbx_pose_optimization_batch(int device, const float *Tcw, const orbx_pose_camera *cams, const orbx_pose_obs *obs,
+                                 const int32_t *offsets, int nproblems, float *Tcw_out, uint8_t *outlier,
+                                 double *chi2, int *n_inliers, int *iterations);
+/* The same on device arrays of the current device, enqueued on `stream` with
+ * no synchronisation.  d_chi2 is required: it is the kernel's per-observation
+ * state between trials as well as an output; d_iterations is nullable.  The
+ * kernel reads nothing it did not write in this launch besides the inputs, so
+ * buffers can be reused across calls as they are. */
+int orbx_pose_optimization_batch_device(const float *d_Tcw, const orbx_pose_camera *d_cams,
+                                        const orbx_pose_obs *d_obs, const int32_t *d_offsets, int nproblems,
+                                        float *d_Tcw_out, uint8_t *d_outlier, double *d_chi2, int32_t *d_n_inliers,
+                                        int32_t *d_iterations, void *stream);
+/* One linear system of a round at the input pose: the normal equations over
+ * the observations with active[i] != 0 (active NULL: all), Huber kernels iff
+ * robust, (H + lambda I) x = b.  H_out[36] row-major, b_out[6], x_out[6],
+ * *chi2_out the robust chi2 sum, *solved = 0 when H + lambda I is not
+ * positive definite (x_out is then zero).  Test hook. */
+int orbx_pose_debug_step(int device, const float *Tcw, const orbx_pose_camera *cam, const orbx_pose_obs *obs, int n,
+                         const uint8_t *active, int robust, double lambda, double *H_out, double *b_out,
+                         double *x_out, double *chi2_out, int *solved);
+
 /* Device evaluation of the restated sincosf / fastAtan2 (test hook). */
 int orbx_debug_trig(int device, const float *angles, float *s, float *c, int n,
                     const float *ys, const float *xs, float *atan_deg, int m);

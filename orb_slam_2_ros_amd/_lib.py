@@ -150,6 +150,10 @@ _SIGNATURES = {
     "orbx_local_ba_fast": (I32, [I32, P, P, I32, P, I32, P, I32, I32, I32, P, P, P, P]),
     "orbx_ba_debug_step": (I32, [I32, P, P, I32, P, I32, P, I32, I32, ctypes.c_double, P, P, P]),
     "orbx_ba_debug_step_fast": (I32, [I32, P, P, I32, P, I32, P, I32, I32, ctypes.c_double, P, P, P]),
+    "orbx_pose_optimization": (I32, [I32, P, P, P, I32, P, P, P, P, P]),
+    "orbx_pose_optimization_batch": (I32, [I32, P, P, P, P, I32, P, P, P, P, P]),
+    "orbx_pose_optimization_batch_device": (I32, [P, P, P, P, I32, P, P, P, P, P, P]),
+    "orbx_pose_debug_step": (I32, [I32, P, P, P, I32, P, I32, ctypes.c_double, P, P, P, P, P]),
 }
 
 # orbx_covis_fn

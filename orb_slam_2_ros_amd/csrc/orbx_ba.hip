@@ -49,16 +49,10 @@
 #include "orbx_device.h"
 #include "orbx_wave.h"
 #include "orbx_ws.h"
+#include "orbx_se3.h"
 
 namespace orbx {
 namespace {
-
-struct Pose {      // SE3Quat: q = (x, y, z, w), t
-    double q[4];
-    double t[3];
-    int32_t free_idx;   // -1: fixed
-    int32_t pad;
-};
 
 struct EdgeD {     // one observation, device copy
     int32_t cam, point, stereo, pad;
@@ -72,70 +66,6 @@ struct EdgeOut {   // per edge, per linearization
     double hpp[36], hll[9], hpl[18];   // hpl: 6 x 3 (pose rows, point cols)
     double bp[6], bl[3];
 };
-
-// Eigen's q * v (Quaternion::_transformVector): uv = 2 (q.vec x v); v + w uv + q.vec x uv
-__host__ __device__ inline void quat_rotate(const double *q, const double *v, double *o) {
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    for (int i = 0; i < 3; ++i) uv[i] = uv[i] + uv[i];
-    const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
-    for (int i = 0; i < 3; ++i) o[i] = v[i] + q[3] * uv[i] + c[i];
-}
-
-__host__ __device__ inline void se3_map(const Pose &T, const double *X, double *o) {
-    quat_rotate(T.q, X, o);
-    for (int i = 0; i < 3; ++i) o[i] = o[i] + T.t[i];
-}
-
-// Eigen's Quaternion::toRotationMatrix
-__host__ __device__ inline void quat_to_R(const double *q, double *R) {
-    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-
-// Eigen's Quaternion(const Matrix3&) (quaternion_base_assign_impl)
-__host__ __device__ inline void R_to_quat(const double *m, double *q) {
-    const double tr = m[0] + m[4] + m[8];
-    if (tr > 0) {
-        double t = sqrt(tr + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (m[7] - m[5]) * t;
-        q[1] = (m[2] - m[6]) * t;
-        q[2] = (m[3] - m[1]) * t;
-    } else {
-        int i = 0;
-        if (m[4] > m[0]) i = 1;
-        if (m[8] > m[3 * i + i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        double t = sqrt(m[3 * i + i] - m[3 * j + j] - m[3 * k + k] + 1.0);
-        q[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
-        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
-        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
-    }
-}
-
-// SE3Quat::normalizeRotation: w >= 0, unit norm
-__host__ __device__ inline void quat_normalize(double *q) {
-    if (q[3] < 0)
-        for (int i = 0; i < 4; ++i) q[i] *= -1;
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int i = 0; i < 4; ++i) q[i] = q[i] / n;
-}
-
-// Eigen's quaternion product a * b
-__host__ __device__ inline void quat_mul(const double *a, const double *b, double *o) {
-    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    o[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    o[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-}
 
 // error of an edge (computeError) and whether the point is in front
 __device__ inline void edge_error(const EdgeD &e, const Pose &T, const double *X, double *err, bool *front) {
@@ -1641,43 +1571,7 @@ __global__ void k_ba_update(Pose *poses, int ncam, double *pts, int npt, const d
     }
     if (i < npt)
         for (int k = 0; k < 3; ++k) pts[3 * (int64_t)i + k] = pts[3 * (int64_t)i + k] + xl[3 * (int64_t)i + k];
-    if (i < ncam && poses[i].free_idx >= 0) {
-        Pose &T = poses[i];
-        const double *u = xp + 6 * T.free_idx;
-        const double w[3] = {u[0], u[1], u[2]}, ups[3] = {u[3], u[4], u[5]};
-        const double theta = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-        const double Om[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-        double O2[9];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) {
-                double acc = 0;
-                for (int k = 0; k < 3; ++k) acc = acc + Om[3 * r + k] * Om[3 * k + c];
-                O2[3 * r + c] = acc;
-            }
-        double R[9], V[9];
-        if (theta < 0.00001) {
-            for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + Om[k] + O2[k];
-            for (int k = 0; k < 9; ++k) V[k] = R[k];
-        } else {
-            const double a = sin(theta) / theta, b = (1 - cos(theta)) / (theta * theta);
-            const double c = (theta - sin(theta)) / pow(theta, 3);
-            for (int k = 0; k < 9; ++k) {
-                R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + a * Om[k] + b * O2[k];
-                V[k] = ((k % 4 == 0) ? 1.0 : 0.0) + b * Om[k] + c * O2[k];
-            }
-        }
-        double qe[4], te[3];
-        R_to_quat(R, qe);
-        for (int r = 0; r < 3; ++r) te[r] = V[3 * r] * ups[0] + V[3 * r + 1] * ups[1] + V[3 * r + 2] * ups[2];
-        quat_normalize(qe);   // SE3Quat(q, t) constructor
-        // (qe, te) * (T.q, T.t): t = te + qe * T.t, q = qe * T.q, normalised
-        double rt[3], qn[4];
-        quat_rotate(qe, T.t, rt);
-        for (int k = 0; k < 3; ++k) T.t[k] = te[k] + rt[k];
-        quat_mul(qe, T.q, qn);
-        quat_normalize(qn);
-        for (int k = 0; k < 4; ++k) T.q[k] = qn[k];
-    }
+    if (i < ncam && poses[i].free_idx >= 0) se3_exp_update(poses[i], xp + 6 * poses[i].free_idx);
 }
 
 }  // namespace
@@ -1686,26 +1580,6 @@ __global__ void k_ba_update(Pose *poses, int ncam, double *pts, int npt, const d
 using namespace orbx;
 
 namespace {
-
-// Converter::toSE3Quat (Converter.cc:37-47): SE3Quat(R, t) from a float Tcw
-void pose_from_cv(const float *T, Pose &p) {
-    double R[9];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) R[3 * r + c] = T[4 * r + c];
-    R_to_quat(R, p.q);
-    quat_normalize(p.q);
-    for (int r = 0; r < 3; ++r) p.t[r] = T[4 * r + 3];
-}
-
-// Converter::toCvMat(SE3Quat): rotation matrix and translation as float
-void pose_to_cv(const Pose &p, float *T) {
-    double R[9];
-    quat_to_R(p.q, R);
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) T[4 * r + c] = (float)R[3 * r + c];
-        T[4 * r + 3] = (float)p.t[r];
-    }
-}
 
 struct Dev {
     uint8_t *base = nullptr;

@@ -3,7 +3,9 @@ over liborbx's GPU bundle adjustment (include/orbx.h).  The
 caller collects the graph (local keyframes, fixed cameras, local map points
 and their observations) exactly as the reference does; this runs the two LM
 passes and returns the optimised poses and points and the observations to
-erase.  GPU only."""
+erase, and of Optimizer::PoseOptimization (Optimizer.cc:265-509), the
+motion-only optimisation of a frame, single or as a batch of frames in one
+kernel launch.  GPU only."""
 from __future__ import annotations
 
 import ctypes
@@ -12,6 +14,7 @@ import numpy as np
 
 from ._lib import check, load, ptr
 from .synth_ba import BA_EDGE_DTYPE
+from .synth_pose import POSE_CAM_DTYPE, POSE_OBS_DTYPE
 
 
 def local_bundle_adjustment(Tcw, fixed, Xw, edges, iters=(5, 10), device: int = 0, fast: bool = False):
@@ -48,3 +51,101 @@ def debug_step(Tcw, fixed, Xw, edges, robust=True, lam=1e-3, device: int = 0, fa
     check(fn(device, ptr(T), ptr(F), len(T), ptr(X), len(X), ptr(E), len(E), int(robust), float(lam), ptr(x),
              ctypes.byref(chi2), ctypes.byref(ok)), "orbx_ba_debug_step")
     return x[:n], chi2.value, bool(ok.value)
+
+
+def _pose_args(Tcw, cams, obs, offsets):
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 3, 4)
+    C = np.ascontiguousarray(cams, POSE_CAM_DTYPE).reshape(-1)
+    O = np.ascontiguousarray(obs, POSE_OBS_DTYPE).reshape(-1)
+    off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+    if len(C) != len(T) or len(off) != len(T) + 1:
+        raise ValueError("pose batch: Tcw, cams and offsets disagree on the number of problems")
+    return T, C, O, off
+
+
+def pose_optimization(Tcw, cam, obs, device: int = 0):
+    """Optimizer::PoseOptimization of one frame.  Tcw (3, 4) f32, cam
+    POSE_CAM_DTYPE (one record), obs POSE_OBS_DTYPE: the features that have a
+    map point, in feature order.  Returns (Tcw_out (3, 4) f32, outlier (n,)
+    bool, chi2 (n,) f64, n_inliers, iterations per round (4,))."""
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(3, 4)
+    C = np.ascontiguousarray(cam, POSE_CAM_DTYPE).reshape(1)
+    O = np.ascontiguousarray(obs, POSE_OBS_DTYPE).reshape(-1)
+    n = len(O)
+    To = np.empty_like(T)
+    out = np.zeros(max(n, 1), np.uint8)
+    chi2 = np.zeros(max(n, 1), np.float64)
+    ninl = ctypes.c_int(0)
+    its = np.zeros(4, np.int32)
+    check(load().orbx_pose_optimization(device, ptr(T), ptr(C), ptr(O), n, ptr(To), ptr(out), ptr(chi2),
+                                        ctypes.byref(ninl), ptr(its)), "orbx_pose_optimization")
+    return To, out[:n].astype(bool), chi2[:n], int(ninl.value), its
+
+
+def pose_optimization_batch(Tcw, cams, obs, offsets, device: int = 0):
+    """A batch of frames in one launch.  Tcw (P, 3, 4) f32, cams (P,)
+    POSE_CAM_DTYPE, obs POSE_OBS_DTYPE in CSR by problem, offsets (P + 1,)
+    int32.  Returns (Tcw_out, outlier (N,) bool, chi2 (N,), n_inliers (P,),
+    iterations (P, 4)) as numpy arrays.
+
+    With torch device tensors (Tcw (P, 3, 4) f32, cams (P, 5) f32, obs (N, 7)
+    f32 in POSE_OBS_DTYPE's field order, offsets (P + 1,) int32) the call is
+    orbx_pose_optimization_batch_device on the tensors' device and torch's
+    current stream, asynchronous, and the results are device tensors (outlier
+    as uint8)."""
+    if hasattr(Tcw, "is_cuda"):
+        return _pose_batch_device(Tcw, cams, obs, offsets)
+    T, C, O, off = _pose_args(Tcw, cams, obs, offsets)
+    P, N = len(T), len(O)
+    if P and int(off[-1]) != N:
+        raise ValueError("pose batch: offsets[-1] != len(obs)")
+    To = np.empty_like(T)
+    out = np.zeros(max(N, 1), np.uint8)
+    chi2 = np.zeros(max(N, 1), np.float64)
+    ninl = np.zeros(max(P, 1), np.int32)
+    its = np.zeros((max(P, 1), 4), np.int32)
+    check(load().orbx_pose_optimization_batch(device, ptr(T), ptr(C), ptr(O), ptr(off), P, ptr(To), ptr(out),
+                                              ptr(chi2), ptr(ninl), ptr(its)), "orbx_pose_optimization_batch")
+    return To, out[:N].astype(bool), chi2[:N], ninl[:P], its[:P]
+
+
+def _pose_batch_device(Tcw, cams, obs, offsets):
+    import torch
+    for t, dt in ((Tcw, torch.float32), (cams, torch.float32), (obs, torch.float32), (offsets, torch.int32)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.device != Tcw.device:
+            raise ValueError("pose batch: contiguous tensors of one device, f32 / f32 / f32 / int32")
+    P = Tcw.shape[0]
+    N = obs.shape[0]
+    if Tcw.numel() != 12 * P or cams.numel() != 5 * P or obs.numel() != 7 * N or offsets.numel() != P + 1:
+        raise ValueError("pose batch: shapes (P, 3, 4), (P, 5), (N, 7), (P + 1,)")
+    dev = Tcw.device
+    with torch.cuda.device(dev):
+        To = torch.empty_like(Tcw)
+        out = torch.empty(max(N, 1), dtype=torch.uint8, device=dev)
+        chi2 = torch.empty(max(N, 1), dtype=torch.float64, device=dev)
+        ninl = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+        its = torch.empty((max(P, 1), 4), dtype=torch.int32, device=dev)
+        obs_p = obs.data_ptr() if N else out.data_ptr()   # (an empty tensor has no storage; nothing reads it)
+        check(load().orbx_pose_optimization_batch_device(
+            Tcw.data_ptr(), cams.data_ptr(), obs_p, offsets.data_ptr(), P, To.data_ptr(), out.data_ptr(),
+            chi2.data_ptr(), ninl.data_ptr(), its.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+            "orbx_pose_optimization_batch_device")
+    return To, out[:N], chi2[:N], ninl[:P], its[:P]
+
+
+def pose_debug_step(Tcw, cam, obs, active=None, robust=True, lam=0.0, device: int = 0):
+    """One linear system of a round at the input pose (test hook): (H (6, 6),
+    b (6,), x (6,), robust chi2, solved)."""
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(3, 4)
+    C = np.ascontiguousarray(cam, POSE_CAM_DTYPE).reshape(1)
+    O = np.ascontiguousarray(obs, POSE_OBS_DTYPE).reshape(-1)
+    A = None if active is None else np.ascontiguousarray(active, np.uint8)
+    if A is not None and len(A) != len(O):
+        raise ValueError("pose step: one active flag per observation")
+    H, b, x = np.zeros((6, 6)), np.zeros(6), np.zeros(6)
+    chi2 = ctypes.c_double(0)
+    ok = ctypes.c_int(0)
+    check(load().orbx_pose_debug_step(device, ptr(T), ptr(C), ptr(O), len(O), ptr(A), int(robust), float(lam),
+                                      ptr(H), ptr(b), ptr(x), ctypes.byref(chi2), ctypes.byref(ok)),
+          "orbx_pose_debug_step")
+    return H, b, x, chi2.value, bool(ok.value)
