@@ -49,8 +49,11 @@ int orbx_device_count(void);
  * in-order pass over the untaken ones ran.  "ba_cmap_oob" -- in the last
  * orbx_local_ba_fast or orbx_ba_debug_step_fast call, the entries of the
  * camera x point map outside [-1, ne) that the dense Schur product skipped,
- * over all its solves (0 unless the map is stale).  ORBX_EINVAL for an
- * unknown name. */
+ * over all its solves (0 unless the map is stale).  "resize_uniform_tiles" /
+ * "resize_fallback_tiles" -- of the plan the thread's last reserve (explicit
+ * or inside a call) left in force: the wave tiles a frame of the per-level
+ * resize kernel that take the scalar row schedule / the per-lane one (both 0
+ * when the plan falls back to the block kernel).  ORBX_EINVAL for an unknown name. */
 int orbx_debug_counter(const char *name, int64_t *value);
 
 /* ---- ORB_SLAM2::ORBextractor ------------------------------------------ */

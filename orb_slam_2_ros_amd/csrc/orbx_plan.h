@@ -72,6 +72,28 @@ struct ResizeRow {
     uint32_t s01;   // s0 | s1 << 16
     uint32_t b01;   // b0 | b1 << 16
 };
+// Plan::rrows holds two sections of 8-byte slots: the rows above (one per
+// entry of ytaps, at lv[l].ytab_off) and one ResizeTileRow (two slots) per row
+// of tiles of each level (at ResizeSched::tile_off + 2 ty).
+// A tile row is phase-uniform (bit 31 of cls) when every lane group of its
+// tiles has all kResizeK rows inside the level, none of its source rows is
+// clamped (src >= 0, src + 1 <= h_src - 1) and the source rows of the groups
+// advance by one shared sequence of steps >= 1.  Then row j of every group
+// reads source rows S0(group) + rel_j and + 1, and reuses row j - 1's second
+// horizontal pass where the step is 1 (bit j of cls, j = 1 .. kResizeK - 1);
+// rel_j is byte j of rel[] (rel_0 = 0).  k_resize_d reads the record with one
+// scalar load and runs such tiles with a scalar row schedule; all other tiles
+// (edges, clamped rows, drifting phases) keep the per-lane schedule.
+struct ResizeTileRow {
+    uint32_t cls;
+    uint32_t rel[3];
+};
+// k_resize_d's launch argument for the row schedule of one level.
+struct ResizeSched {
+    int on = 0;         // some tile row of the level is phase-uniform
+    int tile_off = 0;   // the level's ResizeTileRow records, in slots of rrows
+    int tail_tx = 0;    // tile columns from here on hold scalar-tail column groups (smask != 0xF)
+};
 
 struct LevelGeom {
     int w, h;
@@ -98,7 +120,10 @@ struct LevelGeom {
 // per level to waste the fewest columns at the right edge.  10 rows per lane:
 // at the 1.2 scale factor the source rows advance by 6 every 5 output rows,
 // so every lane group starts at the same phase and the lanes of a wave reuse
-// the previous row's horizontal pass together (resize_tile).
+// the previous row's horizontal pass together.  plan_resize_waves checks that
+// per row of tiles (ResizeTileRow): where it holds exactly (no clamped source
+// row, no row past the level, one step sequence for all groups) k_resize_d
+// takes the row schedule as scalars; elsewhere the lanes keep their own.
 constexpr int kResizeK = 10;
 struct ResizeWave {
     double sx = 0, sy = 0;     // source / destination size ratio, as make_resize_taps
@@ -135,7 +160,9 @@ struct Plan {
     int max_quota = 0;
     std::vector<ResizeWave> rw;   // per level (index 0 unused); empty: k_resize_lds path
     std::vector<ResizeCol> rcols;   // k_resize_d tables (rw[l].col_off; rows at lv[l].ytab_off)
-    std::vector<ResizeRow> rrows;
+    std::vector<ResizeRow> rrows;   // (and the tile rows' records: ResizeTileRow)
+    std::vector<ResizeSched> rs;    // per level, beside rw
+    int resize_uniform_tiles = 0, resize_fallback_tiles = 0;   // k_resize_d tiles a frame, by row schedule
     // Region pyramid (k_pyramid_rgn, small batches): per region 2 x kMaxLevels
     // rectangles, [l] = the level-l pixels it computes (level 0: reads),
     // [kMaxLevels + l] = the ones it owns and writes.  rgn_n = 0: not used.

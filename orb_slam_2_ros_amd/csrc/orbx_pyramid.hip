@@ -347,13 +347,134 @@ __device__ inline void resize_tile_direct(const DevPlan &p, const FrameBufs &fb,
     }
 }
 
-__global__ __launch_bounds__(kThreads) void k_resize_d(DevPlan p, FrameBufs fb, int l, ResizeWave a, int B) {
+// A phase-uniform tile row (ResizeTileRow, plan_resize_waves): every lane
+// group's kResizeK rows lie inside the level, no source row is clamped and the
+// groups' source rows advance by one shared sequence, so the row schedule is
+// the wave's and not the lane's.  A lane keeps two bases (its group's first
+// source row and its first output row, one v_mad each); every row's source and
+// store offsets are scalar multiples of the pitches in the buffer
+// instructions' scalar offset, the reuse of the previous row's horizontal
+// pass is a scalar branch on the shared pattern, there is no y < h test, and
+// the row records are read for their coefficients alone.
+// Scalar branches and not one body per pattern: the patterns of a plan are
+// few at exactly 1.2 but drift with the phase at every other ratio (333 ->
+// 278), and a branch costs two SALU a row beside ~30 VALU.
+// TAIL: the tile holds scalar-tail columns (smask != 0xF); such a wave runs
+// the per-column form alone, every other wave the SSE2 form alone.
+// The arithmetic is resize_tile_direct's: every output byte is the same.
+template <bool TAIL>
+__device__ inline void resize_tile_uniform(const DevPlan &p, const FrameBufs &fb, int l, const ResizeWave &a,
+                                           const ResizeSched &sc, int b, int ty, int tx, int lane, uint32_t cls,
+                                           uint32_t rel0, uint32_t rel1, uint32_t rel2) {
+    const LevelArgs g = p.la[l], gs = p.la[l - 1];
+    const int twg = a.twg, lr = lane >> a.twg_shift, lg = lane & (twg - 1);
+    const int TH = (64 >> a.twg_shift) * kResizeK;
+    const int xb = tx * 4 * twg + 4 * lg, yb = ty * TH + mul24u(lr, kResizeK);
+    if (xb >= g.w) return;
+    const __amdgpu_buffer_rsrc_t ct = wave_rsrc(p.rcols + a.col_off), rt = wave_rsrc(p.rrows + a.ytab_off);
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+    const int co = mul24u(xb, 12);
+    const u32x3 cg0 = __builtin_amdgcn_raw_buffer_load_b96(ct, co, 0, 0);     // c, o, smask
+    const u32x4 cg1 = __builtin_amdgcn_raw_buffer_load_b128(ct, co + 16, 0, 0);   // sel
+    const u32x4 cg2 = __builtin_amdgcn_raw_buffer_load_b128(ct, co + 32, 0, 0);   // coef
+    const uint32_t s01 = __builtin_amdgcn_raw_buffer_load_b32(rt, 8 * yb, 0, 0);   // the group's first row
+    // The vertical coefficients stay packed (b0 | b1 << 16, one VGPR a row, unpacked to b << 12 by
+    // two SDWA shifts a row): as {b0 << 12, b1 << 12} pairs they cost two VALU a row less but ten
+    // VGPRs more (112 against 97), and the kernel's register footprint beside k_fast's waves
+    // outweighs its own VALU in the pipelined step.
+    uint32_t bq[kResizeK];
+#pragma unroll
+    for (int j = 0; j < kResizeK; ++j) bq[j] = __builtin_amdgcn_raw_buffer_load_b32(rt, 8 * yb + 4, 8 * j, 0);
+    int spitch;
+    __amdgpu_buffer_rsrc_t src = wave_rsrc(level_ptr(p, fb, l - 1, b, spitch));
+    spitch = __builtin_amdgcn_readfirstlane(spitch);
+    if (l == 1) {   // (the caller's image: range as in resize_tile_direct)
+        const uint64_t a0 = reinterpret_cast<uint64_t>(level_ptr(p, fb, 0, b, spitch));
+        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a0), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a0 >> 32));
+        src = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(((uint64_t)hi << 32) | lo), (short)0,
+                                                ((gs.h - 1) * spitch + gs.w + 3) & ~3, 0x00020000);
+    }
+    const int c = (int)cg0.x, o = (int)cg0.y;
+    const uint32_t sel[4] = {cg1.x, cg1.y, cg1.z, cg1.w}, coef[4] = {cg2.x, cg2.y, cg2.z, cg2.w};
+    // source row of output row j, relative to the group's first (scalar)
+    auto rel = [&](int j) -> int { return (int)(((j < 4 ? rel0 : j < 8 ? rel1 : rel2) >> (8 * (j & 3))) & 0xFFu); };
+    auto reuse = [&](int j) -> bool { return j > 0 && (cls >> j & 1u) != 0; };
+    const int sbase = mul24u((int)(s01 & 0xFFFFu), spitch) + c;
+    u32x3 d0[kResizeK], d1[kResizeK];
+#pragma unroll
+    for (int j = 0; j < kResizeK; ++j) {
+        const int off = rel(j) * spitch;
+        if (!reuse(j)) d0[j] = __builtin_amdgcn_raw_buffer_load_b96(src, sbase, off, 0);
+        // Only the tile's last row can read the source level's last row, where
+        // the buffer's range has to cut the dword past the image: that one
+        // load carries its row in the lane offset, which the range check covers
+        // whatever it makes of the scalar offset.
+        if (j < kResizeK - 1) d1[j] = __builtin_amdgcn_raw_buffer_load_b96(src, sbase, off + spitch, 0);
+        else d1[j] = __builtin_amdgcn_raw_buffer_load_b96(src, sbase + (off + spitch), 0, 0);
+    }
+    const __amdgpu_buffer_rsrc_t dst = wave_rsrc(fb.pyr + (int64_t)b * p.pyr_bytes + g.pyr_off);
+    const int dbase = mul24u(yb, g.pitch) + xb;
+    auto hrow = [&](u32x3 d, uint32_t h[4]) {
+        const uint32_t w0 = __builtin_amdgcn_alignbyte(d.y, d.x, o), w1 = __builtin_amdgcn_alignbyte(d.z, d.y, o);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t pr = __builtin_amdgcn_perm(w1, w0, sel[k]);
+            h[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2_t, pr), __builtin_bit_cast(u16x2_t, coef[k]), 0u,
+                                          false);
+        }
+    };
+    uint32_t hp[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < kResizeK; ++j) {
+        uint32_t h0[4], h1[4];
+        if (reuse(j)) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) h0[k] = hp[k];
+        } else {
+            hrow(d0[j], h0);
+        }
+        hrow(d1[j], h1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) hp[k] = h1[k];
+        uint32_t packed = 0;
+        if (!TAIL) {
+            packed = resize_vpass_simd(h0, h1, (bq[j] & 0xFFFFu) << 12, (bq[j] >> 16) << 12);
+        } else {
+            const uint32_t smask = cg0.z, b0 = bq[j] & 0xFFFFu, b1 = bq[j] >> 16;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t v = (smask >> k & 1u)
+                                       ? ((mul24u(h0[k] >> 4, b0) >> 16) + (mul24u(h1[k] >> 4, b1) >> 16) + 2) >> 2
+                                       : (mul24u(h0[k], b0) + mul24u(h1[k], b1) + (1 << 21)) >> 22;
+                packed |= v << (8 * k);
+            }
+        }
+        __builtin_amdgcn_raw_buffer_store_b32(packed, dst, dbase, j * g.pitch, 0);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_resize_d(DevPlan p, FrameBufs fb, int l, ResizeWave a, int B, ResizeSched sc) {
     const int wave = wave_id(), lane = threadIdx.x & 63;
     const int L = xcd_logical_block(blockIdx.x, gridDim.x);
     const int t = L * 4 + wave;
     if (t >= a.ntiles * B) return;
-    const int b = t / a.ntiles;
-    resize_tile_direct(p, fb, l, a, b, t - b * a.ntiles, lane);
+    const int b = t / a.ntiles, tile = t - b * a.ntiles;
+    if (sc.on) {
+        // the tile row's class and row schedule: one scalar load from the tile index
+        const int ty = tile / a.ntx, tx = tile - ty * a.ntx;
+        const uint4 tr = *reinterpret_cast<const uint4 *>(p.rrows + sc.tile_off + 2 * ty);
+        uint32_t cls = __builtin_amdgcn_readfirstlane(tr.x), r0 = __builtin_amdgcn_readfirstlane(tr.y),
+                 r1 = __builtin_amdgcn_readfirstlane(tr.z), r2 = __builtin_amdgcn_readfirstlane(tr.w);
+        // (all four words here: one s_load_dwordx4, not the class first and the rows after a second wait)
+        asm volatile("" : "+s"(cls), "+s"(r0), "+s"(r1), "+s"(r2));
+        if (cls >> 31) {
+            if (tx >= sc.tail_tx) resize_tile_uniform<true>(p, fb, l, a, sc, b, ty, tx, lane, cls, r0, r1, r2);
+            else resize_tile_uniform<false>(p, fb, l, a, sc, b, ty, tx, lane, cls, r0, r1, r2);
+            return;
+        }
+    }
+    resize_tile_direct(p, fb, l, a, b, tile, lane);
 }
 
 // ===========================================================================
@@ -464,7 +585,7 @@ hipError_t launch_resize_level(const DevPlan &p, const Plan &hp, const FrameBufs
         const ResizeWave &a = hp.rw[l];
         const int waves = a.ntiles * B;
         if (a.direct) {
-            hipLaunchKernelGGL(k_resize_d, dim3((waves + 3) / 4), dim3(kThreads), 0, st, p, fb, l, a, B);
+            hipLaunchKernelGGL(k_resize_d, dim3((waves + 3) / 4), dim3(kThreads), 0, st, p, fb, l, a, B, hp.rs[l]);
             return hipGetLastError();
         }
         // one global round trip for the whole window: NB >= the staging's row passes
@@ -573,11 +694,17 @@ bool use_pyr_regions(const Plan &hp, int B) { return hp.rgn_n > 0 && (int64_t)B 
 // kernel k_resize then runs instead.
 bool plan_resize_waves(Plan &hp) {
     hp.rw.assign(hp.nlevels, ResizeWave{});
+    hp.rs.assign(hp.nlevels, ResizeSched{});
+    hp.resize_uniform_tiles = hp.resize_fallback_tiles = 0;
+    const char *un = std::getenv("ORBX_RESIZE_UNIFORM");   // =0: the per-lane row schedule for every tile
+    const bool uniform_on = !(un && un[0] == '0');
+    const size_t nrows = hp.ytaps.size();
     for (int l = 1; l < hp.nlevels; ++l) {
         bool direct = hp.lv[l - 1].w >= 8 && !std::getenv("ORBX_RESIZE_LDS");   // =1: windows in LDS
         if (l == 1) {
             hp.rcols.clear();
-            hp.rrows.assign(hp.ytaps.size(), ResizeRow{});
+            // the rows, then the tile rows' records (appended per level)
+            hp.rrows.assign(nrows, ResizeRow{});
         }
         const LevelGeom &g = hp.lv[l], &gs = hp.lv[l - 1];
         const ResizeTap *xt = hp.xtaps.data() + g.xtab_off;
@@ -598,6 +725,7 @@ bool plan_resize_waves(Plan &hp) {
         const int nty = (g.h + TH - 1) / TH;
         a.ntiles = a.ntx * nty;
         int nd_max = 0, nd_win = 0;
+        int tail_tx = INT_MAX;   // first tile column with a scalar-tail column group
         a.col_off = (int)hp.rcols.size();   // one ResizeCol per 4 columns, x / 4
         for (int tx = 0; tx < a.ntx; ++tx) {
             const int x0 = tx * TW, xl = std::min(x0 + TW, g.w) - 1;
@@ -625,6 +753,7 @@ bool plan_resize_waves(Plan &hp) {
                     rc.coef[k] = (uint32_t)(uint16_t)t.a0 | ((uint32_t)(uint16_t)t.a1 << 16);
                     rc.smask |= (t.mode & 2) ? 1 << k : 0;
                 }
+                if (rc.smask != 0xF) tail_tx = std::min(tail_tx, tx);
                 hp.rcols.push_back(rc);
             }
         }
@@ -634,6 +763,39 @@ bool plan_resize_waves(Plan &hp) {
                      (uint32_t)std::min(std::max((int)yt[y].src + 1, 0), gs.h - 1) << 16;
             rr.b01 = ((uint32_t)yt[y].a0 & 0xFFFu) | ((uint32_t)yt[y].a1 & 0xFFFu) << 16;
         }
+        // The tile rows' classes (ResizeTileRow).  Phase-uniform: every lane
+        // group's kResizeK rows inside the level, no source row clamped, and
+        // one sequence of source-row steps (each >= 1) shared by the groups.
+        ResizeSched sc;
+        sc.tile_off = (int)hp.rrows.size();
+        sc.tail_tx = tail_tx;
+        int n_uniform = 0;
+        for (int ty = 0; ty < nty; ++ty) {
+            const int y0 = ty * TH;
+            ResizeTileRow tr{};
+            bool uni = uniform_on && direct && y0 + TH <= g.h;
+            for (int y = y0; uni && y < y0 + TH; ++y) uni = yt[y].src >= 0 && yt[y].src + 1 <= gs.h - 1;
+            for (int lr = 0; uni && lr < TH / kResizeK; ++lr)
+                for (int j = 1; j < kResizeK; ++j) {
+                    const int r0 = yt[y0 + j].src - yt[y0].src;
+                    const int r = yt[y0 + lr * kResizeK + j].src - yt[y0 + lr * kResizeK].src;
+                    const int step = yt[y0 + j].src - yt[y0 + j - 1].src;
+                    if (r != r0 || step < 1 || r0 > 255) { uni = false; break; }
+                    if (lr == 0) {
+                        tr.rel[j >> 2] |= (uint32_t)r0 << (8 * (j & 3));
+                        tr.cls |= step == 1 ? 1u << j : 0u;
+                    }
+                }
+            if (uni) tr.cls |= 1u << 31; else tr = ResizeTileRow{};
+            n_uniform += uni;
+            static_assert(sizeof(ResizeTileRow) == 2 * sizeof(ResizeRow), "a tile row's record is two row slots");
+            hp.rrows.push_back(ResizeRow{tr.cls, tr.rel[0]});
+            hp.rrows.push_back(ResizeRow{tr.rel[1], tr.rel[2]});
+        }
+        sc.on = n_uniform > 0;
+        hp.rs[l] = sc;
+        hp.resize_uniform_tiles += n_uniform * a.ntx;
+        hp.resize_fallback_tiles += (nty - n_uniform) * a.ntx;
         int nr_max = 0;
         for (int ty = 0; ty < nty; ++ty) {
             const int y0 = ty * TH, yl = std::min(y0 + TH, g.h) - 1;

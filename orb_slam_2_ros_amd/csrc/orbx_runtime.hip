@@ -374,9 +374,21 @@ int upload_plan(orbx_extractor *ex) {
     return ORBX_OK;
 }
 
+// Diagnostics of the calling thread's last host call (orbx_debug_counter).
+struct DebugCounters {
+    int64_t bow_repairs = 0;   // SearchByBoW features that took the in-order repair pass (orbx_bow.hip)
+    // k_resize_d tiles a frame of the thread's last extractor plan, by row schedule (plan_resize_waves)
+    int64_t resize_uniform_tiles = 0, resize_fallback_tiles = 0;
+};
+thread_local DebugCounters g_debug;
+
 int reserve(orbx_extractor *ex, int w, int h, int max_batch) {
     if (w < 8 || h < 8 || w > 4095 || h > 4095 || max_batch <= 0) return ORBX_EINVAL;
-    if (ex->planned && ex->plan.width == w && ex->plan.height == h && ex->max_batch >= max_batch) return ORBX_OK;
+    if (ex->planned && ex->plan.width == w && ex->plan.height == h && ex->max_batch >= max_batch) {
+        g_debug.resize_uniform_tiles = ex->plan.resize_uniform_tiles;
+        g_debug.resize_fallback_tiles = ex->plan.resize_fallback_tiles;
+        return ORBX_OK;
+    }
     if (hipSetDevice(ex->device) != hipSuccess) return ORBX_ENODEV;
     (void)hipStreamSynchronize(ex->stream);
     ex->release();
@@ -390,7 +402,12 @@ int reserve(orbx_extractor *ex, int w, int h, int max_batch) {
         if (g.ncols > 0 && g.nrows > 0 && g.nini <= 0) return ORBX_EINVAL;
     }
     if (!resize_window_fits(ex->plan)) return ORBX_EINVAL;
-    if (!plan_resize_waves(ex->plan) || std::getenv("ORBX_RESIZE_BLOCKS")) ex->plan.rw.clear();
+    if (!plan_resize_waves(ex->plan) || std::getenv("ORBX_RESIZE_BLOCKS")) {
+        ex->plan.rw.clear();
+        ex->plan.resize_uniform_tiles = ex->plan.resize_fallback_tiles = 0;   // (no k_resize_d tiles)
+    }
+    g_debug.resize_uniform_tiles = ex->plan.resize_uniform_tiles;
+    g_debug.resize_fallback_tiles = ex->plan.resize_fallback_tiles;
     const char *rg = std::getenv("ORBX_PYR_RGN");   // =0: the per-level resize kernels at every batch
     if (!(rg && rg[0] == '0')) (void)plan_pyr_regions(ex->plan);
     int rc = upload_plan(ex);
@@ -2049,12 +2066,6 @@ int bow_check(int variant, const orbx_bow_side *A, const orbx_bow_side *B, const
     return (A->n == 0 || B->n == 0 || A->nnodes == 0 || B->nnodes == 0) ? 1 : ORBX_OK;
 }
 
-// Diagnostics of the calling thread's last host call (orbx_debug_counter).
-struct DebugCounters {
-    int64_t bow_repairs = 0;   // SearchByBoW features that took the in-order repair pass (orbx_bow.hip)
-};
-thread_local DebugCounters g_debug;
-
 int bow_run(int device, int variant, orbx_bow_problem *P, int np, float nnratio, int check_ori, int nlevels) {
     g_debug.bow_repairs = 0;
     if (np < 0 || (np && !P)) return ORBX_EINVAL;
@@ -2235,6 +2246,8 @@ int orbx_search_by_bow_batch(int device, int variant, orbx_bow_problem *problems
 int orbx_debug_counter(const char *name, int64_t *value) {
     if (!name || !value) return ORBX_EINVAL;
     if (!std::strcmp(name, "bow_repairs")) { *value = g_debug.bow_repairs; return ORBX_OK; }
+    if (!std::strcmp(name, "resize_uniform_tiles")) { *value = g_debug.resize_uniform_tiles; return ORBX_OK; }
+    if (!std::strcmp(name, "resize_fallback_tiles")) { *value = g_debug.resize_fallback_tiles; return ORBX_OK; }
     if (!std::strcmp(name, "ba_cmap_oob")) { *value = orbx::ba_cmap_oob_last(); return ORBX_OK; }
     return ORBX_EINVAL;
 }

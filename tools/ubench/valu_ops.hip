@@ -44,6 +44,9 @@ OPK(max_u32, CH8("v_max_u32_e32", "%8, %0"))
 OPK(min_i32, CH8("v_min_i32_e32", "%8, %0"))
 OPK(mul_u32_u24, CH8("v_mul_u32_u24_e32", "%8, %0"))
 OPK(mul_lo_u32, CH8("v_mul_lo_u32", "%8, %0"))
+// (k_resize_d's vertical pass: eight high halves a row, both operands below 2^24)
+OPK(mul_hi_u32, CH8("v_mul_hi_u32", "%8, %0"))
+OPK(mul_hi_u32_u24, CH8("v_mul_hi_u32_u24_e32", "%8, %0"))
 OPK(add_u32_sgpr, CH8("v_add_u32_e32", "%10, %0"))
 OPK(add_u32_inline, CH8("v_add_u32_e32", "7, %0"))
 OPK(add_u32_literal, CH8("v_add_u32_e32", "0x12345, %0"))
@@ -106,7 +109,7 @@ struct Op { const char *name; void (*k)(uint32_t *, uint64_t *, int, uint32_t, u
 #define EF(N) {#N, k_##N, ONE, 0u}
 static const Op kOps[] = {
     E(add_u32), E(sub_u32), E(and_b32), E(or_b32), E(xor_b32), E(lshrrev_b32), E(lshlrev_b32), E(min_u32), E(max_u32),
-    E(min_i32), E(mul_u32_u24), E(mul_lo_u32), E(add_u32_sgpr), E(add_u32_inline), E(add_u32_literal),
+    E(min_i32), E(mul_u32_u24), E(mul_lo_u32), E(mul_hi_u32), E(mul_hi_u32_u24), E(add_u32_sgpr), E(add_u32_inline), E(add_u32_literal),
     E(and_b32_literal), E(add3_u32), E(lshl_add_u32), E(lshl_or_b32), E(and_or_b32), E(or3_b32), E(xad_u32),
     E(min3_u32), E(max3_u32), E(med3_u32), E(mad_u32_u24), E(bfe_u32), E(bfi_b32), E(alignbyte_b32),
     E(alignbit_b32), E(perm_b32_vsel), E(perm_b32_ssel), E(sad_u8), E(sad_u32), E(msad_u8), E(cndmask_b32),
