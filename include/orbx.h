@@ -53,7 +53,15 @@ int orbx_device_count(void);
  * "resize_fallback_tiles" -- of the plan the thread's last reserve (explicit
  * or inside a call) left in force: the wave tiles a frame of the per-level
  * resize kernel that take the scalar row schedule / the per-lane one (both 0
- * when the plan falls back to the block kernel).  ORBX_EINVAL for an unknown name. */
+ * when the plan falls back to the block kernel).  "proj_hard" / "proj_pool_used" /
+ * "proj_rounds" / "proj_in_order" / "proj_full_list" -- of the greedy replay of
+ * the last orbx_search_by_projection(_batch) call's first non-empty problem
+ * (Fuse has no replay: 0): the (keypoint, query) claims registered by queries
+ * with more than 4 entries within th_dist (more than 4 * nq + 4096 of them
+ * send every query to the in-order pass), the entries of the candidate-list
+ * pool the call used (all its problems), the parallel rounds run (64 at most),
+ * the queries the rounds left to the in-order pass, and the full-list scans
+ * the rounds ran (512 a round at most).  ORBX_EINVAL for an unknown name. */
 int orbx_debug_counter(const char *name, int64_t *value);
 
 /* ---- ORB_SLAM2::ORBextractor ------------------------------------------ */

@@ -306,6 +306,10 @@ def search_by_projection(variant, keys, desc, queries, qdesc, bounds, uright=Non
     qdist = np.full(max(len(q), 1), -1, np.int32)
     kf = np.full(max(len(keys), 1), -1, np.int32)
     v = PROJ_VARIANTS[variant] if isinstance(variant, str) else int(variant)
+    if v == PROJ_VARIANTS["fuse"] and len(keys) and (isg is None or keys["octave"].min() < 0
+                                                      or keys["octave"].max() >= len(isg)):
+        # Fuse indexes invSigma2 by the keypoint's octave (ORBmatcher.cc:905-930) and the entry carries no length
+        raise ValueError("fuse: a keypoint octave outside inv_sigma2")
     nm = lib().orbo_search_by_projection(v, _p(keys), _p(desc), None if ur is None else _p(ur),
                                          None if ms is None else _p(ms), None if isg is None else _p(isg),
                                          len(keys), *[float(b) for b in bounds], _p(q), _p(qd), len(q),

@@ -1191,7 +1191,7 @@ void for_common_nodes(const BowView &A, const BowView &B, F f) {
 }
 
 bool check_dist_epipolar_line(const orbo_keypoint &kp1, const orbo_keypoint &kp2, const float *F12,
-                              const float *sigma2_2) {
+                              float sigma2) {
     const float a = kp1.x * F12[0] + kp1.y * F12[3] + F12[6];
     const float b = kp1.x * F12[1] + kp1.y * F12[4] + F12[7];
     const float c = kp1.x * F12[2] + kp1.y * F12[5] + F12[8];
@@ -1199,7 +1199,7 @@ bool check_dist_epipolar_line(const orbo_keypoint &kp1, const orbo_keypoint &kp2
     const float den = a * a + b * b;
     if (den == 0) return false;
     const float dsqr = num * num / den;
-    return dsqr < 3.84 * sigma2_2[kp2.octave];
+    return dsqr < 3.84 * sigma2;
 }
 
 }  // namespace
@@ -1236,11 +1236,14 @@ int orbo_search_by_bow(int variant, const orbo_keypoint *ka, const uint8_t *da, 
                     const int dist = hamming32(da + 32 * (size_t)i1, db + 32 * (size_t)i2);
                     if (dist > TH_LOW || dist > bestDist) continue;
                     const orbo_keypoint &kp2 = kb[i2];
+                    // an octave outside [0, nlevels) has no table entry (the reference reads past
+                    // mvScaleFactors / mvLevelSigma2): both count as 0, as in liborbx, so the pair is rejected
+                    const bool lv = kp2.octave >= 0 && kp2.octave < nlevels;
                     if (!bStereo1 && !bStereo2) {
                         const float distex = ex - kp2.x, distey = ey - kp2.y;
-                        if (distex * distex + distey * distey < 100 * scale2[kp2.octave]) continue;
+                        if (distex * distex + distey * distey < 100 * (lv ? scale2[kp2.octave] : 0.0f)) continue;
                     }
-                    if (check_dist_epipolar_line(ka[i1], kp2, F12, sigma2)) { bestIdx2 = i2; bestDist = dist; }
+                    if (check_dist_epipolar_line(ka[i1], kp2, F12, lv ? sigma2[kp2.octave] : 0.0f)) { bestIdx2 = i2; bestDist = dist; }
                 }
                 if (bestIdx2 >= 0) {
                     match_a[i1] = bestIdx2;

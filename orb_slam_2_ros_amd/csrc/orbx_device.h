@@ -188,6 +188,9 @@ struct ProjBufs {
     uint2 *hard; int hard_cap;               // (keypoint, query) claims past a query's 4 kept entries
     uint8_t *und;                            // nq: 0 decided, 1 open, 2 left to the in-order replay
     int32_t *stats;                          // optional: rounds, queries replayed in order
+    // optional, zeroed by the caller, copied back with the outputs: rounds run,
+    // queries replayed in order, full-list scans the rounds ran (orbx_debug_counter)
+    int32_t *ctr;
     int nblk;                                // search blocks of this problem (proj_blocks(nq))
 };
 

@@ -316,9 +316,13 @@ __device__ __attribute__((always_inline)) void proj_search(const ProjBufs *pa, u
             }
         } else {
             if (claims && top[3] != kNone && e_dist(top[3]) <= a.th_dist && list) {
-                // more possible takes than the 4 kept: register them all (rare)
+                // the 4 kept are all possible takes: with a fifth, register them all (rare)
                 __threadfence();
-                for (int t = lane; t < T; t += 64) {
+                int within = 0;
+                for (int t = lane; t < T; t += 64)
+                    within += e_dist(__hip_atomic_load(list + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) <= a.th_dist;
+                within = wave_sum_i32(within);
+                for (int t = lane; within > 4 && t < T; t += 64) {
                     const uint32_t ent = __hip_atomic_load(list + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if (e_dist(ent) <= a.th_dist) {
                         const uint32_t h = atomicAdd(a.hard_cnt, 1u);
@@ -483,7 +487,7 @@ __device__ __attribute__((always_inline)) void proj_replay(const ProjBufs &a, ui
     // ---- 3a. rounds of order-independent decisions
     // (claims lost to a full `hard` list: everything goes in order)
     if (!fuse && nhard <= (uint32_t)a.hard_cap) {
-        int accepted = 0;
+        int accepted = 0, rounds_run = 0, nfull = 0;
         for (int round = 0; round < 64; ++round) {
             for (int i = tid; i < n; i += kPT) opn[i] = kNone;
             if (tid == 0) { sh_prog[round & 1] = 0; sh_fq = 0; }
@@ -493,6 +497,7 @@ __device__ __attribute__((always_inline)) void proj_replay(const ProjBufs &a, ui
                 if (a.stats && tid == 0) a.stats[0] = round;
                 break;
             }
+            rounds_run = round + 1;
             for (int q = tid; q < nq; q += kPT) {
                 if (qs[q] != (1 | 4)) continue;   // open and blocking (other takes close nothing)
                 const uint4 t4 = qt[q];
@@ -546,6 +551,7 @@ __device__ __attribute__((always_inline)) void proj_replay(const ProjBufs &a, ui
             }
             __syncthreads();
             const int nfq = min(sh_fq, kFQ);
+            nfull += nfq;
             for (int i = wave; i < nfq; i += kPW) {
                 const int q = fq[3 * i], qb = fq[3 * i + 1], len = fq[3 * i + 2];
                 const int st = qs[q];
@@ -575,6 +581,7 @@ __device__ __attribute__((always_inline)) void proj_replay(const ProjBufs &a, ui
         }
         const int tot = wave_sum_i32(accepted);
         if (lane == 0 && tot) atomicAdd(&sh_acc, tot);
+        if (a.ctr && tid == 0) { a.ctr[0] = rounds_run; a.ctr[2] = nfull; }
         __syncthreads();
     }
     if (a.stats && tid == 0) a.stats[3] = (int)(wall_clock64() - c0);
@@ -625,6 +632,7 @@ __device__ __attribute__((always_inline)) void proj_replay(const ProjBufs &a, ui
         }
         if (lane == 0) sh_acc += accepted;
         if (a.stats && lane == 0) a.stats[1] = nserial;
+        if (a.ctr && lane == 0) a.ctr[1] = nserial;
     }
     __syncthreads();
     if (a.stats && tid == 0) a.stats[5] = (int)(wall_clock64() - c0);

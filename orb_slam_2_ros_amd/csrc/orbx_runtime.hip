@@ -379,6 +379,9 @@ struct DebugCounters {
     int64_t bow_repairs = 0;   // SearchByBoW features that took the in-order repair pass (orbx_bow.hip)
     // k_resize_d tiles a frame of the thread's last extractor plan, by row schedule (plan_resize_waves)
     int64_t resize_uniform_tiles = 0, resize_fallback_tiles = 0;
+    // replay of the last projection call's first non-empty problem (orbx_proj.hip): `hard` claims registered,
+    // list-pool entries used (all problems), rounds run, queries left to the in-order pass, full-list scans
+    int64_t proj_hard = 0, proj_pool_used = 0, proj_rounds = 0, proj_in_order = 0, proj_full_list = 0;
 };
 thread_local DebugCounters g_debug;
 
@@ -1876,6 +1879,7 @@ struct CallClock {
 };
 
 int proj_run(int device, int variant, orbx_proj_problem *P, int np, int th_dist, float nnratio, int check_ori) {
+    g_debug.proj_hard = g_debug.proj_pool_used = g_debug.proj_rounds = g_debug.proj_in_order = g_debug.proj_full_list = 0;
     if (np < 0 || (np && !P)) return ORBX_EINVAL;
     CallClock clk;   // (ORBX_CALL_TIMING: checks / staging / enqueue / wait / readback)
     std::vector<int> live;
@@ -1919,8 +1923,10 @@ int proj_run(int device, int variant, orbx_proj_problem *P, int np, int th_dist,
             o[t].qd = L.add(32 * (size_t)pr.nq);
         }
         const size_t o_pa = L.add(sizeof(ProjBufs) * nl);
-        // pool_top, then hard_cnt per problem, then the HostTail counter: zeros from the host
-        const size_t o_cnt = L.add(16 + 8 * (size_t)nl);
+        // pool_top, then hard_cnt per problem, then the HostTail counter, then problem 0's
+        // replay counters (rounds, in order, full-list scans): zeros from the host
+        const size_t cnt_bytes = 16 + 8 * (size_t)nl + 16, o_ctr = 16 + 8 * (size_t)nl;
+        const size_t o_cnt = L.add(cnt_bytes);
         const size_t in_bytes = L.size;
         for (int t = 0; t < nl; ++t) {
             const int n = P[live[t]].frame.n, nq = P[live[t]].nq;
@@ -1967,10 +1973,11 @@ int proj_run(int device, int variant, orbx_proj_problem *P, int np, int th_dist,
             a.pool_top = at<unsigned long long>(D, o_cnt); a.hard_cnt = at<uint32_t>(D, o_cnt + 8 + 8 * (size_t)t);
             a.hard = at<uint2>(D, o[t].hard); a.hard_cap = o[t].hard_cap; a.und = D + o[t].und;
             a.stats = dbg_stats && t == 0 ? at<int32_t>(D, o_stats) : nullptr;
+            a.ctr = t == 0 ? at<int32_t>(D, o_cnt + o_ctr) : nullptr;
             a.nblk = proj_blocks(nq);
         }
         put(ws, o_pa, hb.data(), sizeof(ProjBufs) * nl);
-        std::memset(ws.host + o_cnt, 0, 16 + 8 * (size_t)nl);
+        std::memset(ws.host + o_cnt, 0, cnt_bytes);
         clk.mark();
         if (hipMemcpyAsync(D, ws.host, in_bytes, hipMemcpyHostToDevice, ws.st) != hipSuccess) return ORBX_EIO;
         // Outputs: one copy whose completion the host polls (ORBX_PROJ_TAIL=2,
@@ -1996,6 +2003,14 @@ int proj_run(int device, int variant, orbx_proj_problem *P, int np, int th_dist,
             if (hipMemcpy(st2, D + o_stats, sizeof(st2), hipMemcpyDeviceToHost) == hipSuccess)
                 std::fprintf(stderr, "orbx proj: variant %d problems %d rounds %d in-order %d pool %llu | 10ns: init %d rounds %d end %d\n",
                              variant, nl, st2[0], st2[1], used, st2[2], st2[3], st2[5]);
+        }
+        {
+            uint32_t nhard = 0;
+            int32_t ctr[3] = {};
+            get(ws, o_cnt + 8, &nhard, 4);
+            get(ws, o_cnt + o_ctr, ctr, sizeof(ctr));
+            g_debug.proj_hard = nhard; g_debug.proj_pool_used = (int64_t)used;
+            g_debug.proj_rounds = ctr[0]; g_debug.proj_in_order = ctr[1]; g_debug.proj_full_list = ctr[2];
         }
         if (!fuse) ws.proj_pool = std::max<int64_t>(ws.proj_pool, (int64_t)used);
         if (!fuse && (int64_t)used > pool) {
@@ -2248,6 +2263,11 @@ int orbx_debug_counter(const char *name, int64_t *value) {
     if (!std::strcmp(name, "bow_repairs")) { *value = g_debug.bow_repairs; return ORBX_OK; }
     if (!std::strcmp(name, "resize_uniform_tiles")) { *value = g_debug.resize_uniform_tiles; return ORBX_OK; }
     if (!std::strcmp(name, "resize_fallback_tiles")) { *value = g_debug.resize_fallback_tiles; return ORBX_OK; }
+    if (!std::strcmp(name, "proj_hard")) { *value = g_debug.proj_hard; return ORBX_OK; }
+    if (!std::strcmp(name, "proj_pool_used")) { *value = g_debug.proj_pool_used; return ORBX_OK; }
+    if (!std::strcmp(name, "proj_rounds")) { *value = g_debug.proj_rounds; return ORBX_OK; }
+    if (!std::strcmp(name, "proj_in_order")) { *value = g_debug.proj_in_order; return ORBX_OK; }
+    if (!std::strcmp(name, "proj_full_list")) { *value = g_debug.proj_full_list; return ORBX_OK; }
     if (!std::strcmp(name, "ba_cmap_oob")) { *value = orbx::ba_cmap_oob_last(); return ORBX_OK; }
     return ORBX_EINVAL;
 }

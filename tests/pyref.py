@@ -244,13 +244,18 @@ def hamming(a: np.ndarray, b: np.ndarray) -> int:
     return int(np.unpackbits(np.bitwise_xor(a, b)).sum())
 
 
-def search_for_initialization(k1, d1, k2, d2, w, h, prev, window, nnratio, check_ori):
+def search_for_initialization(k1, d1, k2, d2, w, h, prev, window, nnratio, check_ori, bounds=None, trace=None):
+    """bounds: (mnMinX, mnMaxX, mnMinY, mnMaxY) of Frame::ComputeImageBounds
+    (Frame.cc:475-499; None: 0, w, 0, h).  trace: a list that receives, per F1
+    feature with candidates, (i1, [(i2, dist, vMatchedDistance[i2] at its turn)])
+    (:462 skips i2 when that is <= dist), and ("steal", i1, loser) on a steal."""
     GC, GR, HL = 64, 48, 30
-    invw, invh = f32(f32(GC) / f32(w)), f32(f32(GR) / f32(h))
+    mnx, mxx, mny, mxy = [f32(b) for b in (bounds if bounds is not None else (0, w, 0, h))]
+    invw, invh = f32(f32(GC) / f32(mxx - mnx)), f32(f32(GR) / f32(mxy - mny))   # Frame.cc:218-219
     grid = {}
     for i, kp in enumerate(k2):
-        px = int(round_half_away(f32(kp["x"] * invw)))
-        py = int(round_half_away(f32(kp["y"] * invh)))
+        px = int(round_half_away(f32(f32(kp["x"] - mnx) * invw)))                # Frame.cc:417-418
+        py = int(round_half_away(f32(f32(kp["y"] - mny) * invh)))
         if 0 <= px < GC and 0 <= py < GR:
             grid.setdefault((px, py), []).append(i)
     m12 = [-1] * len(k1)
@@ -263,10 +268,10 @@ def search_for_initialization(k1, d1, k2, d2, w, h, prev, window, nnratio, check
         if k1[i1]["octave"] > 0:
             continue
         x, y = f32(prev[i1, 0]), f32(prev[i1, 1])
-        cx0 = max(0, math.floor(f32(f32(x - r) * invw)))
-        cx1 = min(GC - 1, math.ceil(f32(f32(x + r) * invw)))
-        cy0 = max(0, math.floor(f32(f32(y - r) * invh)))
-        cy1 = min(GR - 1, math.ceil(f32(f32(y + r) * invh)))
+        cx0 = max(0, math.floor(f32(f32(f32(x - mnx) - r) * invw)))              # Frame.cc:361-381
+        cx1 = min(GC - 1, math.ceil(f32(f32(f32(x - mnx) + r) * invw)))
+        cy0 = max(0, math.floor(f32(f32(f32(y - mny) - r) * invh)))
+        cy1 = min(GR - 1, math.ceil(f32(f32(f32(y - mny) + r) * invh)))
         cand = []
         if cx0 < GC and cx1 >= 0 and cy0 < GR and cy1 >= 0:
             for ix in range(cx0, cx1 + 1):
@@ -279,8 +284,12 @@ def search_for_initialization(k1, d1, k2, d2, w, h, prev, window, nnratio, check
         if not cand:
             continue
         best, best2, bi = 2 ** 31 - 1, 2 ** 31 - 1, -1
+        seen = []
+        if trace is not None:
+            trace.append((i1, seen))
         for i2 in cand:
             dist = hamming(d1[i1], d2[i2])
+            seen.append((i2, dist, mdist[i2]))
             if mdist[i2] <= dist:
                 continue
             if dist < best:
@@ -290,6 +299,8 @@ def search_for_initialization(k1, d1, k2, d2, w, h, prev, window, nnratio, check
         if best <= 50 and f32(best) < f32(f32(best2) * f32(nnratio)):
             if m21[bi] >= 0:
                 m12[m21[bi]] = -1
+                if trace is not None:
+                    trace.append(("steal", i1, m21[bi]))
             m12[i1], m21[bi], mdist[bi] = bi, i1, best
             if check_ori:
                 rv = f32(k1[i1]["angle"] - k2[bi]["angle"])
@@ -651,7 +662,10 @@ def _area(keys, g, x, y, r, min_level, max_level):
 
 
 def search_by_projection(variant, keys, desc, q, qdesc, bounds, uright=None, mp_state=None, inv_sigma2=None,
-                         th_dist=100, nnratio=0.6, check_ori=True):
+                         th_dist=100, nnratio=0.6, check_ori=True, trace=None):
+    """trace: a list that receives, per active query with candidates,
+    (iq, [(idx, dist, free)]) in GetFeaturesInArea order: free says the
+    keypoint passed the query's skip rules at its turn (not taken, gates)."""
     g = _grid(keys, bounds)
     n = len(keys)
     has = [bool(mp_state[i] & 1) if mp_state is not None else False for i in range(n)]
@@ -667,14 +681,19 @@ def search_by_projection(variant, keys, desc, q, qdesc, bounds, uright=None, mp_
         cand = _area(keys, g, Q["u"], Q["v"], Q["radius"], int(Q["min_level"]), int(Q["max_level"]))
         if not cand:
             continue
+        seen = []
+        if trace is not None:
+            trace.append((iq, seen))
         if variant == "localmap":                      # ORBmatcher.cc:45-129
             bd, bl, bd2, bl2, bi = 256, -1, 256, -1, -1
             for idx in cand:
+                seen.append((idx, hamming(qdesc[iq], desc[idx]), False))
                 if has[idx] and obs[idx]:
                     continue
                 if uright is not None and uright[idx] > 0 and abs(f32(Q["ur"] - uright[idx])) > Q["ur_tol"]:
                     continue
                 d = hamming(qdesc[iq], desc[idx])
+                seen[-1] = (idx, d, True)
                 if d < bd:
                     bd2, bd, bl2, bl, bi = bd, d, bl, int(keys["octave"][idx]), idx
                 elif d < bd2:
@@ -688,6 +707,7 @@ def search_by_projection(variant, keys, desc, q, qdesc, bounds, uright=None, mp_
             continue
         bd, bi = (2 ** 31 - 1 if variant == "fuse_sim3" else 256), -1
         for idx in cand:
+            seen.append((idx, hamming(qdesc[iq], desc[idx]), False))
             if variant == "lastframe":                 # :1403-1413
                 if has[idx] and obs[idx]:
                     continue
@@ -710,6 +730,7 @@ def search_by_projection(variant, keys, desc, q, qdesc, bounds, uright=None, mp_
                     if float(f32(e2 * inv_sigma2[lvl])) > 5.99:
                         continue
             d = hamming(qdesc[iq], desc[idx])
+            seen[-1] = (idx, d, True)
             if d < bd:
                 bd, bi = d, idx
         if bd <= th_dist:
@@ -750,6 +771,39 @@ def search_by_projection(variant, keys, desc, q, qdesc, bounds, uright=None, mp_
     return nm, np.array(q_idx, np.int32), np.array(q_dist, np.int32), np.array(kp_final, np.int32)
 
 
+# ---- SearchBySim3 (ORBmatcher.cc:1104-1328) on per-slot query tables ----------
+def search_by_sim3(k1, d1, b1, k2, d2, b2, q1, qd1, q2, qd2, th_dist=100, trace=None):
+    """q1[i1]: map point i1 of KF1 projected into KF2 (flags bit 0 clear: one of
+    the reference's skips, :1154-1185), q2 the other way.  Each side keeps its
+    best keypoint in the window (:1193-1226, INT_MAX start, octave in
+    [min_level, max_level] = [predicted - 1, predicted], '<= TH_HIGH'); a pair
+    stays when both sides chose each other (:1309-1325).  trace receives
+    (vnMatch1, vnMatch2)."""
+    def side(keys, desc, bounds, q, qd):
+        g = _grid(keys, bounds)
+        out = [-1] * len(q)
+        for i in range(len(q)):
+            Q = q[i]
+            if not (Q["flags"] & 1):
+                continue
+            bd, bi = 2 ** 31 - 1, -1
+            for idx in _area(keys, g, Q["u"], Q["v"], Q["radius"], -1, -1):   # KeyFrame::GetFeaturesInArea: no levels
+                if keys["octave"][idx] < Q["min_level"] or keys["octave"][idx] > Q["max_level"]:
+                    continue
+                d = hamming(qd[i], desc[idx])
+                if d < bd:
+                    bd, bi = d, idx
+            if bd <= th_dist:
+                out[i] = bi
+        return out
+    m1 = side(k2, d2, b2, q1, qd1)
+    m2 = side(k1, d1, b1, q2, qd2)
+    if trace is not None:
+        trace.append((m1, m2))
+    m12 = [m1[i] if m1[i] >= 0 and m2[m1[i]] == i else -1 for i in range(len(q1))]
+    return sum(m >= 0 for m in m12), np.array(m12, np.int32)
+
+
 # ---- SearchByBoW x2 / SearchForTriangulation (ORBmatcher.cc:160-289, 524-825) ----
 def search_by_bow(variant, A, B, nnratio=0.6, check_ori=True, tri=None, nlevels=8):
     na, nb = len(A["keys"]), len(B["keys"])
@@ -772,7 +826,8 @@ def search_by_bow(variant, A, B, nnratio=0.6, check_ori=True, tri=None, nlevels=
         if den == 0:
             return False
         dsqr = f32(f32(num * num) / den)
-        return float(dsqr) < 3.84 * float(f32(sigma2[k2["octave"]]))
+        lv = 0 <= k2["octave"] < nlevels        # no table entry outside: 0, as liborbx and the oracle take it
+        return float(dsqr) < 3.84 * float(f32(sigma2[k2["octave"]]) if lv else 0.0)
 
     for i, nid in enumerate(A["ids"]):
         j = idsB.get(int(nid))
@@ -796,7 +851,8 @@ def search_by_bow(variant, A, B, nnratio=0.6, check_ori=True, tri=None, nlevels=
                     k2 = B["keys"][i2]
                     if not st1 and not st2:
                         dx, dy = f32(ex - f32(k2["x"])), f32(ey - f32(k2["y"]))
-                        if f32(f32(dx * dx) + f32(dy * dy)) < f32(f32(100) * f32(scale2[k2["octave"]])):
+                        sc = f32(scale2[k2["octave"]]) if 0 <= k2["octave"] < nlevels else f32(0)
+                        if f32(f32(dx * dx) + f32(dy * dy)) < f32(f32(100) * sc):
                             continue
                     if epi_ok(A["keys"][i1], k2):
                         bi, bd = i2, d
