@@ -682,6 +682,77 @@ int orbx_pose_debug_step(int device, const float *Tcw, const orbx_pose_camera *c
                          const uint8_t *active, int robust, double lambda, double *H_out, double *b_out,
                          double *x_out, double *chi2_out, int *solved);
 
+/* ---- Optimizer::OptimizeSim3 (Optimizer.cc:1177-1414) ------------------------
+ * The relative Sim3 between two keyframes of a loop candidate: one free
+ * VertexSim3Expmap, an EdgeSim3ProjectXYZ and an EdgeInverseSim3ProjectXYZ per
+ * correspondence (both with g2o's numeric Jacobian, central differences with
+ * delta = 1e-9, and a Huber kernel), two rounds of Levenberg-Marquardt with
+ * the classification between them.  The whole optimisation of a problem is
+ * one wave of one kernel launch (k_sim3_optimize); DESIGN.md §3.14 is the
+ * numeric specification. */
+typedef struct orbx_sim3 {  /* 64 bytes: the members of g2o::Sim3 */
+    double q[4];            /* rotation().coeffs(): x, y, z, w (not normalised) */
+    double t[3];            /* translation() */
+    double s;               /* scale() */
+} orbx_sim3;
+
+typedef struct orbx_sim3_camera {  /* 16 bytes */
+    float fx, fy, cx, cy;          /* K(0,0), K(1,1), K(0,2), K(1,2) */
+} orbx_sim3_camera;
+
+typedef struct orbx_sim3_corr {  /* 48 bytes */
+    float P1c[3];                /* R1w * P3D1w + t1w (:1265) */
+    float P2c[3];                /* R2w * P3D2w + t2w (:1274) */
+    float u1, v1, inv_sigma2_1;  /* pKF1->mvKeysUn[i].pt, mvInvLevelSigma2[octave] */
+    float u2, v2, inv_sigma2_2;  /* pKF2->mvKeysUn[i2].pt, mvInvLevelSigma2[octave] */
+} orbx_sim3_corr;
+
+/* One candidate.  corr: the n correspondences in vnIndexEdge's order.
+ * S12_out: g2oS12 after the call (a byte copy of S12 when fewer than ten
+ * correspondences survive the first classification, where the reference
+ * returns before it writes g2oS12); removed[n]: 0 kept, 1 removed by the
+ * first classification, 2 by the second; chi2_12[n], chi2_21[n] (nullable):
+ * each edge's last computed chi2; *n_inliers: the return value;
+ * iterations[2] (nullable): LM iterations run per round.  Host arrays,
+ * synchronous. */
+int orbx_optimize_sim3(int device, const orbx_sim3 *S12, const orbx_sim3_camera *cam1, const orbx_sim3_camera *cam2,
+                       const orbx_sim3_corr *corr, int n, float th2, int fix_scale, orbx_sim3 *S12_out,
+                       uint8_t *removed, double *chi2_12, double *chi2_21, int *n_inliers, int *iterations);
+/* nproblems candidates at once: S12, cam1, cam2, th2, fix_scale and S12_out
+ * hold one element per problem, problem p's correspondences are
+ * corr[offsets[p] .. offsets[p + 1]) (offsets[0] = 0, ascending); removed and
+ * the chi2 arrays (nullable) in the same layout, n_inliers[nproblems],
+ * iterations[nproblems][2] (nullable).  One upload, one launch, one download;
+ * synchronous. */
+int orbx_optimize_sim3_batch(int device, const orbx_sim3 *S12, const orbx_sim3_camera *cam1,
+                             const orbx_sim3_camera *cam2, const orbx_sim3_corr *corr, const int32_t *offsets,
+                             int nproblems, const float *th2, const int32_t *fix_scale, orbx_sim3 *S12_out,
+                             uint8_t *removed, double *chi2_12, double *chi2_21, int *n_inliers, int *iterations);
+/* The same on device arrays of the current device, enqueued on `stream` with
+ * no synchronisation.  d_chi2_12 and d_chi2_21 are required: they are the
+ * kernel's per-correspondence state between trials as well as outputs;
+ * d_iterations is nullable.  The kernel reads nothing it did not write in this
+ * launch besides the inputs, so buffers can be reused across calls. */
+int orbx_optimize_sim3_batch_device(const orbx_sim3 *d_S12, const orbx_sim3_camera *d_cam1,
+                                    const orbx_sim3_camera *d_cam2, const orbx_sim3_corr *d_corr,
+                                    const int32_t *d_offsets, int nproblems, const float *d_th2,
+                                    const int32_t *d_fix_scale, orbx_sim3 *d_S12_out, uint8_t *d_removed,
+                                    double *d_chi2_12, double *d_chi2_21, int32_t *d_n_inliers,
+                                    int32_t *d_iterations, void *stream);
+/* One linear system at S12: the normal equations over the correspondences
+ * with active[i] != 0 (active NULL: all), Huber kernels iff robust,
+ * (H + lambda I) x = b.  H_out[49] row-major, b_out[7], x_out[7], *chi2_out
+ * the robust chi2 sum, *solved = 0 when H + lambda I is not positive definite
+ * (x_out is then zero).  Test hook. */
+int orbx_sim3_debug_step(int device, const orbx_sim3 *S12, const orbx_sim3_camera *cam1,
+                         const orbx_sim3_camera *cam2, const orbx_sim3_corr *corr, int n, float th2, int fix_scale,
+                         const uint8_t *active, int robust, double lambda, double *H_out, double *b_out,
+                         double *x_out, double *chi2_out, int *solved);
+/* S_out[k] = Sim3(x[k]) * S[k] for count update vectors x[count][7] (x[6]
+ * zeroed first when fix_scale): the update of a trial.  Test hook. */
+int orbx_sim3_debug_update(int device, const orbx_sim3 *S, const double *x, int count, int fix_scale,
+                           orbx_sim3 *S_out);
+
 /* Device evaluation of the restated sincosf / fastAtan2 (test hook). */
 int orbx_debug_trig(int device, const float *angles, float *s, float *c, int n,
                     const float *ys, const float *xs, float *atan_deg, int m);

@@ -154,6 +154,11 @@ _SIGNATURES = {
     "orbx_pose_optimization_batch": (I32, [I32, P, P, P, P, I32, P, P, P, P, P]),
     "orbx_pose_optimization_batch_device": (I32, [P, P, P, P, I32, P, P, P, P, P, P]),
     "orbx_pose_debug_step": (I32, [I32, P, P, P, I32, P, I32, ctypes.c_double, P, P, P, P, P]),
+    "orbx_optimize_sim3": (I32, [I32, P, P, P, P, I32, F32, I32, P, P, P, P, P, P]),
+    "orbx_optimize_sim3_batch": (I32, [I32, P, P, P, P, P, I32, P, P, P, P, P, P, P, P]),
+    "orbx_optimize_sim3_batch_device": (I32, [P, P, P, P, P, I32, P, P, P, P, P, P, P, P, P]),
+    "orbx_sim3_debug_step": (I32, [I32, P, P, P, P, I32, F32, I32, P, I32, ctypes.c_double, P, P, P, P, P]),
+    "orbx_sim3_debug_update": (I32, [I32, P, P, I32, I32, P]),
 }
 
 # orbx_covis_fn
