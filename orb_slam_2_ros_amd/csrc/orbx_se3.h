@@ -1,8 +1,10 @@
 // orbx_se3.h -- g2o's SE3Quat as the optimisers hold it (se3quat.h), shared by
-// orbx_ba.hip (local bundle adjustment) and orbx_pose.hip (pose optimisation):
+// orbx_ba.hip (local bundle adjustment), orbx_pose.hip (pose optimisation) and
+// orbx_sim3.h (the quaternion products of g2o's Sim3):
 // Eigen's quaternion conversions and products in its operation order, the
-// exponential update exp(dx) * T, and Converter::toSE3Quat / toCvMat.  Both
-// files compile this one text, so a pose takes the same roundings in both.
+// exponential update exp(dx) * T, and Converter::toSE3Quat / toCvMat.  All of
+// them compile this one text, so a pose takes the same roundings in each.  The
+// optimisers' Levenberg-Marquardt control and solve are orbx_lm.h's, not here.
 #pragma once
 
 #include <hip/hip_runtime.h>

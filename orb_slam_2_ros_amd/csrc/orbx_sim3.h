@@ -3,29 +3,30 @@
 // compile (tools/sim3_host/sim3_host.cpp, the CPU figure and a CPU parity
 // check): g2o's Sim3 (sim3.h) without its Eigen types, the two reprojection
 // edges of a correspondence, their numeric Jacobians (base_binary_edge.hpp:
-// 147-200, central differences with delta = 1e-9), the 7x7 system and its
-// Cholesky, the update and the Levenberg-Marquardt control.
+// 147-200, central differences with delta = 1e-9), the update and the two
+// rounds.  The 7x7 system's sums, its Cholesky, Huber and the Levenberg-
+// Marquardt control are orbx_lm.h's with N = 7, the text pose optimisation runs.
 //
 // Whatever differs between the device and the host is behind an executor X:
-//   X::build(S, H, b, &chi)   the normal equations over the active set at S
-//   X::errors(S)              the robust chi2 over the active set at S
+// orbx_lm.h's build / errors / update (update is sim3_update with the
+// problem's fix_scale), and
 //   X::classify(mark)         flags the active correspondences over th2
 // The device's executor spreads the correspondences over the 64 lanes of a
 // wave and folds the lanes' partials through LDS; the host's runs the lanes
 // one after another.  Both add in §3.14's order, so they agree bit for bit.
 #pragma once
 
-#include <cfloat>
 #include <cmath>
 #include <cstdint>
 
+#include "orbx_lm.h"
 #include "orbx_se3.h"
 #include "../../include/orbx.h"
 
 namespace orbx {
 
-constexpr int kSim3Lanes = 64;
-constexpr int kSim3Sums = 36;    // H(a, b) a <= b: 28, b: 7, robust chi2: 1
+constexpr int kSim3Lanes = kLmLanes;
+constexpr int kSim3Sums = lm_sums(7);   // H(a, b) a <= b: 28, b: 7, robust chi2: 1
 constexpr int kSim3Table = 15;   // the estimate and its 14 perturbations
 
 struct Sim3 {   // g2o::Sim3: r = (x, y, z, w) (never normalised), t, s
@@ -248,20 +249,6 @@ __host__ __device__ inline double sim3_chi2(const double *e, double omega) {
     return chi2;
 }
 
-// RobustKernelHuber::robustify (rho0, rho1); without a kernel (chi2, 1)
-__host__ __device__ inline void sim3_huber(double chi2, bool robust, double delta, double &rho0, double &rho1) {
-    rho0 = chi2;
-    rho1 = 1.0;
-    if (robust) {
-        const double dsqr = delta * delta;
-        if (!(chi2 <= dsqr)) {
-            const double s = sqrt(chi2);
-            rho0 = 2 * s * delta - dsqr;
-            rho1 = delta / s;
-        }
-    }
-}
-
 // One problem as the lanes see it.  A correspondence is active iff
 // (flag[i] != 0) == sense: the removal flags with sense = false, or the step
 // hook's active array with sense = true (flag == nullptr: all active).
@@ -327,28 +314,8 @@ __host__ __device__ inline double sim3_edge_terms(const Table &tab, bool inv, co
     }
     const double chi2 = sim3_chi2(e, omega);
     double rho0, rho1;
-    sim3_huber(chi2, robust, delta, rho0, rho1);
-    const double w = rho1 * omega;   // robustInformation
-    const double omr[2] = {-(omega * e[0]) * rho1, -(omega * e[1]) * rho1};
-    int idx = 0;
-#pragma unroll
-    for (int i = 0; i < 7; ++i)
-#pragma unroll
-        for (int j = i; j < 7; ++j) {
-            double t = 0;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) t = t + (J[k][i] * w) * J[k][j];
-            acc[idx] = acc[idx] + t;
-            ++idx;
-        }
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        double t = 0;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) t = t + J[k][i] * omr[k];
-        acc[28 + i] = acc[28 + i] + t;
-    }
-    acc[35] = acc[35] + rho0;
+    lm_huber(chi2, robust, delta, rho0, rho1);
+    lm_edge_sums(J, e, omega, rho0, rho1, acc);
     return chi2;
 }
 
@@ -377,11 +344,11 @@ __host__ __device__ inline double sim3_lane_errors(const Sim3Problem &pr, const 
         double e[2], rho0, rho1;
         sim3_edge_error(S, P2, pr.c1, (double)c.u1, (double)c.v1, e);
         const double c12 = sim3_chi2(e, (double)c.inv_sigma2_1);
-        sim3_huber(c12, pr.robust, pr.delta, rho0, rho1);
+        lm_huber(c12, pr.robust, pr.delta, rho0, rho1);
         acc = acc + rho0;
         sim3_edge_error(Sinv, P1, pr.c2, (double)c.u2, (double)c.v2, e);
         const double c21 = sim3_chi2(e, (double)c.inv_sigma2_2);
-        sim3_huber(c21, pr.robust, pr.delta, rho0, rho1);
+        lm_huber(c21, pr.robust, pr.delta, rho0, rho1);
         acc = acc + rho0;
         pr.chi12[i] = c12;
         pr.chi21[i] = c21;
@@ -389,136 +356,20 @@ __host__ __device__ inline double sim3_lane_errors(const Sim3Problem &pr, const 
     return acc;
 }
 
-// The folded sums as H (7x7, mirrored), b and the robust chi2
-__host__ __device__ inline void sim3_unpack(const double *tot, double *H, double *b, double *chi) {
-    int idx = 0;
-#pragma unroll
-    for (int i = 0; i < 7; ++i)
-#pragma unroll
-        for (int j = i; j < 7; ++j) {
-            H[7 * i + j] = tot[idx];
-            H[7 * j + i] = tot[idx];
-            ++idx;
-        }
-#pragma unroll
-    for (int i = 0; i < 7; ++i) b[i] = tot[28 + i];
-    *chi = tot[35];
-}
-
-// (H + lambda I) x = b by a 7x7 Cholesky, k_ba_chol's conventions (pose_solve
-// with one more row); false if not positive definite
-__host__ __device__ inline bool sim3_solve(const double *H, const double *b, double lambda, double *x) {
-    double L[49];
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-        double d = H[7 * j + j] + lambda;
-#pragma unroll
-        for (int k = 0; k < j; ++k) d = d - L[7 * j + k] * L[7 * j + k];
-        if (!(d > 0)) return false;
-        const double diag = sqrt(d);
-        L[7 * j + j] = diag;
-#pragma unroll
-        for (int i = j + 1; i < 7; ++i) {
-            double s = H[7 * i + j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s = s - L[7 * i + k] * L[7 * j + k];
-            L[7 * i + j] = s / diag;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {   // L y = b
-        double s = b[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s = s - L[7 * i + k] * x[k];
-        x[i] = s / L[7 * i + i];
-    }
-#pragma unroll
-    for (int i = 6; i >= 0; --i) {   // L^T x = y
-        double s = x[i];
-#pragma unroll
-        for (int k = 6; k > i; --k) s = s - L[7 * k + i] * x[k];
-        x[i] = s / L[7 * i + i];
-    }
-    return true;
-}
-
-// optimize(maxit) of one round: pose_lm (orbx_pose.hip) statement for
-// statement with seven dimensions.  Returns the iterations run.
-template <class X>
-__host__ __device__ inline int sim3_lm(X &ex, Sim3 &S, int fix_scale, int maxit) {
-    double lambda = 0, ni = 2, currentChi = 0;
-    int nBad = 0;
-    for (int it = 0; it < 10; ++it) {
-        if (it >= maxit) return maxit;
-        double H[49], b[7];
-        ex.build(S, H, b, &currentChi);
-        if (it == 0) {
-            double mx = 0.;
-#pragma unroll
-            for (int j = 0; j < 7; ++j) {   // std::max(fabs(H_jj), mx)
-                const double a = fabs(H[8 * j]);
-                mx = a < mx ? mx : a;
-            }
-            lambda = 1e-5 * mx;   // _tau * maxDiagonal
-            ni = 2;
-            nBad = 0;
-        }
-        const double iniChi = currentChi;
-        double rho = 0;
-        int qmax = 0;
-        do {
-            double x[7];
-            const bool ok = sim3_solve(H, b, lambda, x);
-            const Sim3 bk = S;
-            double tempChi = DBL_MAX;
-            double sc = 0.0;
-            if (ok) {   // (a failed solve leaves the estimate and the errors alone)
-                sim3_update(S, x, fix_scale);
-                tempChi = ex.errors(S);
-#pragma unroll
-                for (int j = 0; j < 7; ++j) sc += x[j] * (lambda * x[j] + b[j]);   // computeScale
-            }
-            rho = currentChi - tempChi;
-            sc += 1e-3;
-            rho /= sc;
-            if (rho > 0 && std::isfinite(tempChi)) {
-                const double t = 2 * rho - 1;
-                double alpha = 1. - t * t * t;
-                alpha = (2. / 3.) < alpha ? (2. / 3.) : alpha;                      // std::min(alpha, 2/3)
-                const double scaleFactor = (1. / 3.) < alpha ? alpha : (1. / 3.);   // std::max(1/3, alpha)
-                lambda *= scaleFactor;
-                ni = 2;
-                currentChi = tempChi;
-            } else {
-                lambda *= ni;
-                ni *= 2;
-                if (ok) S = bk;   // pop()
-            }
-            qmax++;
-        } while (rho < 0 && qmax < 10);
-        if (qmax == 10 || rho == 0) return it + 1;   // Terminate
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++;
-        else nBad = 0;
-        if (nBad >= 3) return it + 1;
-    }
-    return 10;
-}
-
 // Optimizer.cc:1337-1413: two rounds with the classification between them.
 // Sout is S0 itself unless both rounds ran.
 template <class X>
-__host__ __device__ inline void sim3_optimize(X &ex, const Sim3 &S0, int n, int fix_scale, Sim3 &Sout, int &n_inliers,
-                                              int *its) {
+__host__ __device__ inline void sim3_optimize(X &ex, const Sim3 &S0, int n, Sim3 &Sout, int &n_inliers, int *its) {
     its[0] = 0;
     its[1] = 0;
     n_inliers = 0;
     Sout = S0;
     if (n == 0) return;
     Sim3 S = S0;
-    its[0] = sim3_lm(ex, S, fix_scale, 5);
+    its[0] = lm_run<7>(ex, S, 5);
     const int nBad = ex.classify(1);
     if (n - nBad < 10) return;   // :1379, before g2oS12 is written
-    its[1] = sim3_lm(ex, S, fix_scale, nBad > 0 ? 10 : 5);
+    its[1] = lm_run<7>(ex, S, nBad > 0 ? 10 : 5);
     const int nOut = ex.classify(2);
     n_inliers = n - nBad - nOut;
     Sout = S;

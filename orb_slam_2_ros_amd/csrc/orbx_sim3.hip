@@ -6,7 +6,8 @@
 // numerically (central differences, delta = 1e-9), and so does this kernel:
 // 30 projections per correspondence and linearisation.  DESIGN.md §3.14 is
 // the numeric specification, orbx_sim3.h its text (shared with a host
-// compile), tests/pyref_sim3.py its numpy restatement.
+// compile; the LM control, the solve and the lanes' fold are orbx_lm.h's, shared
+// with orbx_pose.hip), tests/pyref_sim3.py its numpy restatement.
 //
 //   k_sim3_optimize   one wave (one 64-thread workgroup) per problem, the
 //                     whole optimisation in the one launch.  Per
@@ -35,40 +36,22 @@
 
 #include "orbx_device.h"
 #include "orbx_sim3.h"
+#include "orbx_ws.h"
 
 namespace orbx {
 namespace {
 
 struct Sim3Lds {
-    double part[kSim3Lanes * kSim3Sums];
-    double tot[kSim3Sums];
+    LmFoldLds<kSim3Sums> fold;
     Sim3 tab[kSim3Table], tabinv[kSim3Table];
 };
 
-// The device's executor of orbx_sim3.h's sim3_lm / sim3_optimize
+// The device's executor of orbx_lm.h's lm_run and orbx_sim3.h's sim3_optimize
 struct Sim3Wave {
     Sim3Problem pr;
     uint8_t *flags;
     int lane;
     Sim3Lds *lds;
-
-    // The partials of the wave's lanes, added in lane order: tot[f] = ((P_0 + P_1) + P_2) + ... + P_63
-    template <int NF>
-    __device__ inline void fold(const double *acc, double *tot) {
-        Sim3Lds &s = *lds;
-#pragma unroll
-        for (int f = 0; f < NF; ++f) s.part[lane * kSim3Sums + f] = acc[f];
-        __syncthreads();
-        if (lane < NF) {
-            double a = s.part[lane];
-            for (int l = 1; l < kSim3Lanes; ++l) a = a + s.part[l * kSim3Sums + lane];
-            s.tot[lane] = a;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int f = 0; f < NF; ++f) tot[f] = s.tot[f];
-        __syncthreads();   // (the next fold writes part and tot again)
-    }
 
     __device__ inline void build(const Sim3 &S, double *H, double *b, double *chi) {
         if (lane < kSim3Table) {   // the linearisation's table, once for the wave
@@ -84,8 +67,9 @@ struct Sim3Wave {
         for (int f = 0; f < kSim3Sums; ++f) acc[f] = 0.0;
         sim3_lane_build(pr, ref, lane, acc);
         double tot[kSim3Sums];
-        fold<kSim3Sums>(acc, tot);   // (its barriers also keep the table until every lane is done with it)
-        sim3_unpack(tot, H, b, chi);
+        // (the fold's barriers also keep the table until every lane is done with it)
+        lm_fold<kSim3Sums>(lds->fold, acc, lane, tot);
+        lm_unpack<7>(tot, H, b, chi);
     }
 
     __device__ inline double errors(const Sim3 &S) {
@@ -93,9 +77,11 @@ struct Sim3Wave {
         sim3_inverse(S, Sinv);
         double acc[1] = {sim3_lane_errors(pr, S, Sinv, lane)};
         double tot[1];
-        fold<1>(acc, tot);
+        lm_fold<1>(lds->fold, acc, lane, tot);
         return tot[0];
     }
+
+    __device__ inline void update(Sim3 &S, const double *x) { sim3_update(S, x, pr.fix_scale); }
 
     __device__ inline int classify(int mark) {
         int bad = 0;
@@ -158,7 +144,7 @@ __global__ __launch_bounds__(kSim3Lanes) void k_sim3_optimize(
     const Sim3 S0 = sim3_load(S12 + p);
     Sim3 out;
     int nin, its[2];
-    sim3_optimize(ex, S0, n, ex.pr.fix_scale, out, nin, its);
+    sim3_optimize(ex, S0, n, out, nin, its);
     if (lane == 0) {
         sim3_store(out, S12_out + p);
         n_inliers[p] = nin;
@@ -193,7 +179,7 @@ __global__ __launch_bounds__(kSim3Lanes) void k_sim3_step(const orbx_sim3 *S12, 
     ex.lds = &lds;
     double H[49], b[7], chi, x[7];
     ex.build(sim3_load(S12), H, b, &chi);
-    const bool ok = sim3_solve(H, b, lambda, x);
+    const bool ok = lm_solve<7>(H, b, lambda, x);
     if (threadIdx.x == 0) {
         for (int j = 0; j < 49; ++j) res[j] = H[j];
         for (int j = 0; j < 7; ++j) res[49 + j] = b[j];
@@ -215,45 +201,10 @@ __global__ __launch_bounds__(kSim3Lanes) void k_sim3_update(const orbx_sim3 *S, 
     }
 }
 
-// Per-device workspace of the host entry points, kept across calls: the
-// stream, a device arena and a pinned staging buffer, grown on demand.
-struct Sim3Ws {
-    std::mutex mu;
-    hipStream_t st = nullptr;
-    uint8_t *dev = nullptr, *host = nullptr;
-    size_t cap = 0, hcap = 0;
-};
-
-Sim3Ws &sim3_ws(int device) {
-    static Sim3Ws ws[64];
+// Per-device workspace of the host entry points, kept across calls
+ArenaWs &sim3_ws(int device) {
+    static ArenaWs ws[64];
     return ws[device & 63];
-}
-
-int sim3_ws_reserve(Sim3Ws &ws, size_t bytes) {
-    if (!ws.st && hipStreamCreateWithFlags(&ws.st, hipStreamNonBlocking) != hipSuccess) return ORBX_EIO;
-    if (bytes > ws.cap) {
-        if (ws.dev) (void)hipFree(ws.dev);
-        ws.dev = nullptr;
-        ws.cap = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&ws.dev), bytes) != hipSuccess) return ORBX_ENOMEM;
-        ws.cap = bytes;
-    }
-    if (bytes > ws.hcap) {
-        if (ws.host) (void)hipHostFree(ws.host);
-        ws.host = nullptr;
-        ws.hcap = 0;
-        if (hipHostMalloc(reinterpret_cast<void **>(&ws.host), bytes, hipHostMallocDefault) != hipSuccess)
-            return ORBX_ENOMEM;
-        ws.hcap = bytes;
-    }
-    return ORBX_OK;
-}
-
-size_t sim3_pad(size_t b) { return (b + 255) & ~size_t(255); }
-
-template <class T>
-T *at(uint8_t *base, size_t off) {
-    return reinterpret_cast<T *>(base + off);
 }
 
 }  // namespace
@@ -293,26 +244,25 @@ int orbx_optimize_sim3_batch(int device, const orbx_sim3 *S12, const orbx_sim3_c
     const size_t P = nproblems, N = offsets[nproblems];
     if (N && (!corr || !removed)) return ORBX_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return ORBX_ENODEV;
-    Sim3Ws &ws = sim3_ws(device);
+    ArenaWs &ws = sim3_ws(device);
     std::lock_guard<std::mutex> lock(ws.mu);
     // arena: inputs (one upload), then outputs (one download)
-    const size_t o_S = 0, o_c1 = o_S + sim3_pad(sizeof(orbx_sim3) * P);
-    const size_t o_c2 = o_c1 + sim3_pad(sizeof(orbx_sim3_camera) * P);
-    const size_t o_th = o_c2 + sim3_pad(sizeof(orbx_sim3_camera) * P), o_fix = o_th + sim3_pad(4 * P);
-    const size_t o_off = o_fix + sim3_pad(4 * P), o_corr = o_off + sim3_pad(4 * (P + 1));
-    const size_t in_end = o_corr + sim3_pad(sizeof(orbx_sim3_corr) * (N + 1));
-    const size_t o_So = in_end, o_ni = o_So + sim3_pad(sizeof(orbx_sim3) * P), o_it = o_ni + sim3_pad(4 * P);
-    const size_t o_a = o_it + sim3_pad(8 * P), o_b = o_a + sim3_pad(8 * (N + 1));
-    const size_t o_rm = o_b + sim3_pad(8 * (N + 1)), end = o_rm + sim3_pad(N + 1);
-    int rc = sim3_ws_reserve(ws, end);
+    Layout L;
+    const size_t o_S = L.add(sizeof(orbx_sim3) * P), o_c1 = L.add(sizeof(orbx_sim3_camera) * P);
+    const size_t o_c2 = L.add(sizeof(orbx_sim3_camera) * P), o_th = L.add(4 * P), o_fix = L.add(4 * P);
+    const size_t o_off = L.add(4 * (P + 1)), o_corr = L.add(sizeof(orbx_sim3_corr) * (N + 1));
+    const size_t in_end = L.size;
+    const size_t o_So = L.add(sizeof(orbx_sim3) * P), o_ni = L.add(4 * P), o_it = L.add(8 * P);
+    const size_t o_a = L.add(8 * (N + 1)), o_b = L.add(8 * (N + 1)), o_rm = L.add(N + 1);
+    int rc = ws_reserve(ws, L.size);
     if (rc) return rc;
-    std::memcpy(ws.host + o_S, S12, sizeof(orbx_sim3) * P);
-    std::memcpy(ws.host + o_c1, cam1, sizeof(orbx_sim3_camera) * P);
-    std::memcpy(ws.host + o_c2, cam2, sizeof(orbx_sim3_camera) * P);
-    std::memcpy(ws.host + o_th, th2, 4 * P);
-    std::memcpy(ws.host + o_fix, fix_scale, 4 * P);
-    std::memcpy(ws.host + o_off, offsets, 4 * (P + 1));
-    if (N) std::memcpy(ws.host + o_corr, corr, sizeof(orbx_sim3_corr) * N);
+    put(ws, o_S, S12, sizeof(orbx_sim3) * P);
+    put(ws, o_c1, cam1, sizeof(orbx_sim3_camera) * P);
+    put(ws, o_c2, cam2, sizeof(orbx_sim3_camera) * P);
+    put(ws, o_th, th2, 4 * P);
+    put(ws, o_fix, fix_scale, 4 * P);
+    put(ws, o_off, offsets, 4 * (P + 1));
+    put(ws, o_corr, corr, sizeof(orbx_sim3_corr) * N);
     if (hipMemcpyAsync(ws.dev, ws.host, in_end, hipMemcpyHostToDevice, ws.st) != hipSuccess) return ORBX_EIO;
     uint8_t *d = ws.dev;
     rc = orbx_optimize_sim3_batch_device(at<orbx_sim3>(d, o_S), at<orbx_sim3_camera>(d, o_c1),
@@ -321,15 +271,15 @@ int orbx_optimize_sim3_batch(int device, const orbx_sim3 *S12, const orbx_sim3_c
                                          at<orbx_sim3>(d, o_So), d + o_rm, at<double>(d, o_a), at<double>(d, o_b),
                                          at<int32_t>(d, o_ni), at<int32_t>(d, o_it), ws.st);
     if (rc) return rc;
-    if (hipMemcpyAsync(ws.host + o_So, d + o_So, end - o_So, hipMemcpyDeviceToHost, ws.st) != hipSuccess ||
+    if (hipMemcpyAsync(ws.host + o_So, d + o_So, L.size - o_So, hipMemcpyDeviceToHost, ws.st) != hipSuccess ||
         hipStreamSynchronize(ws.st) != hipSuccess)
         return ORBX_EIO;
-    std::memcpy(S12_out, ws.host + o_So, sizeof(orbx_sim3) * P);
-    std::memcpy(n_inliers, ws.host + o_ni, 4 * P);
-    if (iterations) std::memcpy(iterations, ws.host + o_it, 8 * P);
-    if (N && chi2_12) std::memcpy(chi2_12, ws.host + o_a, 8 * N);
-    if (N && chi2_21) std::memcpy(chi2_21, ws.host + o_b, 8 * N);
-    if (N) std::memcpy(removed, ws.host + o_rm, N);
+    get(ws, o_So, S12_out, sizeof(orbx_sim3) * P);
+    get(ws, o_ni, n_inliers, 4 * P);
+    get(ws, o_it, iterations, 8 * P);
+    get(ws, o_a, chi2_12, 8 * N);
+    get(ws, o_b, chi2_21, 8 * N);
+    get(ws, o_rm, removed, N);
     return ORBX_OK;
 }
 
@@ -349,20 +299,21 @@ int orbx_sim3_debug_step(int device, const orbx_sim3 *S12, const orbx_sim3_camer
     if (n < 0 || !S12 || !cam1 || !cam2 || (n && !corr) || !H_out || !b_out || !x_out || !chi2_out || !solved)
         return ORBX_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return ORBX_ENODEV;
-    Sim3Ws &ws = sim3_ws(device);
+    ArenaWs &ws = sim3_ws(device);
     std::lock_guard<std::mutex> lock(ws.mu);
     const size_t N = n;
-    const size_t o_S = 0, o_c1 = o_S + 256, o_c2 = o_c1 + 256, o_corr = o_c2 + 256;
-    const size_t o_act = o_corr + sim3_pad(sizeof(orbx_sim3_corr) * (N + 1)), in_end = o_act + sim3_pad(N + 1);
-    const size_t o_res = in_end, o_a = o_res + sim3_pad(8 * 65), o_b = o_a + sim3_pad(8 * (N + 1));
-    const size_t end = o_b + sim3_pad(8 * (N + 1));
-    int rc = sim3_ws_reserve(ws, end);
+    Layout L;
+    const size_t o_S = L.add(sizeof(orbx_sim3)), o_c1 = L.add(sizeof(orbx_sim3_camera));
+    const size_t o_c2 = L.add(sizeof(orbx_sim3_camera)), o_corr = L.add(sizeof(orbx_sim3_corr) * (N + 1));
+    const size_t o_act = L.add(N + 1), in_end = L.size;
+    const size_t o_res = L.add(8 * 65), o_a = L.add(8 * (N + 1)), o_b = L.add(8 * (N + 1));
+    int rc = ws_reserve(ws, L.size);
     if (rc) return rc;
-    std::memcpy(ws.host + o_S, S12, sizeof(orbx_sim3));
-    std::memcpy(ws.host + o_c1, cam1, sizeof(orbx_sim3_camera));
-    std::memcpy(ws.host + o_c2, cam2, sizeof(orbx_sim3_camera));
-    if (N) std::memcpy(ws.host + o_corr, corr, sizeof(orbx_sim3_corr) * N);
-    if (N && active) std::memcpy(ws.host + o_act, active, N);
+    put(ws, o_S, S12, sizeof(orbx_sim3));
+    put(ws, o_c1, cam1, sizeof(orbx_sim3_camera));
+    put(ws, o_c2, cam2, sizeof(orbx_sim3_camera));
+    put(ws, o_corr, corr, sizeof(orbx_sim3_corr) * N);
+    put(ws, o_act, active, N);
     if (hipMemcpyAsync(ws.dev, ws.host, in_end, hipMemcpyHostToDevice, ws.st) != hipSuccess) return ORBX_EIO;
     uint8_t *d = ws.dev;
     hipLaunchKernelGGL(k_sim3_step, dim3(1), dim3(kSim3Lanes), 0, ws.st, at<orbx_sim3>(d, o_S),
@@ -388,15 +339,16 @@ int orbx_sim3_debug_update(int device, const orbx_sim3 *S, const double *x, int 
     if (count == 0) return ORBX_OK;
     if (!S || !x || !S_out) return ORBX_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return ORBX_ENODEV;
-    Sim3Ws &ws = sim3_ws(device);
+    ArenaWs &ws = sim3_ws(device);
     std::lock_guard<std::mutex> lock(ws.mu);
     const size_t C = count;
-    const size_t o_S = 0, o_x = o_S + sim3_pad(sizeof(orbx_sim3) * C), in_end = o_x + sim3_pad(56 * C);
-    const size_t o_out = in_end, end = o_out + sim3_pad(sizeof(orbx_sim3) * C);
-    int rc = sim3_ws_reserve(ws, end);
+    Layout L;
+    const size_t o_S = L.add(sizeof(orbx_sim3) * C), o_x = L.add(56 * C), in_end = L.size;
+    const size_t o_out = L.add(sizeof(orbx_sim3) * C);
+    int rc = ws_reserve(ws, L.size);
     if (rc) return rc;
-    std::memcpy(ws.host + o_S, S, sizeof(orbx_sim3) * C);
-    std::memcpy(ws.host + o_x, x, 56 * C);
+    put(ws, o_S, S, sizeof(orbx_sim3) * C);
+    put(ws, o_x, x, 56 * C);
     if (hipMemcpyAsync(ws.dev, ws.host, in_end, hipMemcpyHostToDevice, ws.st) != hipSuccess) return ORBX_EIO;
     uint8_t *d = ws.dev;
     hipLaunchKernelGGL(k_sim3_update, dim3(1), dim3(kSim3Lanes), 0, ws.st, at<orbx_sim3>(d, o_S), at<double>(d, o_x),
@@ -406,7 +358,7 @@ int orbx_sim3_debug_update(int device, const orbx_sim3 *S, const double *x, int 
             hipSuccess ||
         hipStreamSynchronize(ws.st) != hipSuccess)
         return ORBX_EIO;
-    std::memcpy(S_out, ws.host + o_out, sizeof(orbx_sim3) * C);
+    get(ws, o_out, S_out, sizeof(orbx_sim3) * C);
     return ORBX_OK;
 }
 

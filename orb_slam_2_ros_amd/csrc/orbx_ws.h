@@ -1,5 +1,6 @@
 // orbx_ws.h -- per-device workspace of the synchronous host entry points
-// (the drop-in matchers, depth calls and per-frame helpers).
+// (the drop-in matchers, depth calls and per-frame helpers: CallWs; the
+// batched optimisers: ArenaWs) and the arena layout both use.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -82,15 +83,50 @@ inline int ws_reserve(CallWs &ws, size_t bytes) {
 void ws_tail(CallWs &ws, size_t off, size_t bytes, uint32_t *done_d, int blocks, HostTail &t);
 int ws_wait(CallWs &ws, const HostTail &t, size_t off, size_t bytes);
 
+// Workspace of the batched optimisers' host entry points (orbx_pose.hip,
+// orbx_sim3.hip): a stream, a device arena and a pinned staging arena, each
+// grown to the exact size a call needs.  Each optimiser keeps its own per-device
+// array of these (Tracking and LoopClosing call them concurrently, and neither
+// shares the matchers' lock).
+struct ArenaWs {
+    std::mutex mu;
+    hipStream_t st = nullptr;
+    uint8_t *dev = nullptr, *host = nullptr;
+    size_t cap = 0, hcap = 0;
+};
+
+// Ensures stream and capacity (caller holds ws.mu and has set the device).
+inline int ws_reserve(ArenaWs &ws, size_t bytes) {
+    if (!ws.st && hipStreamCreateWithFlags(&ws.st, hipStreamNonBlocking) != hipSuccess) return ORBX_EIO;
+    if (bytes > ws.cap) {
+        if (ws.dev) (void)hipFree(ws.dev);
+        ws.dev = nullptr;
+        ws.cap = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&ws.dev), bytes) != hipSuccess) return ORBX_ENOMEM;
+        ws.cap = bytes;
+    }
+    if (bytes > ws.hcap) {
+        if (ws.host) (void)hipHostFree(ws.host);
+        ws.host = nullptr;
+        ws.hcap = 0;
+        if (hipHostMalloc(reinterpret_cast<void **>(&ws.host), bytes, hipHostMallocDefault) != hipSuccess)
+            return ORBX_ENOMEM;
+        ws.hcap = bytes;
+    }
+    return ORBX_OK;
+}
+
 template <typename T>
 inline T *at(uint8_t *base, size_t off) { return reinterpret_cast<T *>(base + off); }
 
-inline void put(CallWs &ws, size_t off, const void *src, size_t bytes) {
+// (Ws: CallWs or ArenaWs)
+template <typename Ws>
+inline void put(Ws &ws, size_t off, const void *src, size_t bytes) {
     if (bytes && src) std::memcpy(ws.host + off, src, bytes);
 }
-inline void get(CallWs &ws, size_t off, void *dst, size_t bytes) {
+template <typename Ws>
+inline void get(Ws &ws, size_t off, void *dst, size_t bytes) {
     if (bytes && dst) std::memcpy(dst, ws.host + off, bytes);
 }
-
 
 }  // namespace orbx

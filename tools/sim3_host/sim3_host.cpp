@@ -1,5 +1,6 @@
-// sim3_host.cpp -- orbx_sim3.h compiled for the host, one thread: the project's
-// restatement of Optimizer::OptimizeSim3 on a CPU.  The
+// sim3_host.cpp -- orbx_sim3.h, and orbx_lm.h under it, compiled for the host,
+// one thread: the project's restatement of Optimizer::OptimizeSim3 (DESIGN.md
+// §3.14) on a CPU.  The
 // executor runs the 64 lanes of the device's wave one after another and adds
 // their partials in lane order, so the results equal the device's bit for bit
 // (the update's sin / cos are the host's libm here).  tools/sim3_probe.py
@@ -30,7 +31,7 @@ struct HostExec {
             sim3_lane_build(pr, ref, l, acc);
             for (int f = 0; f < kSim3Sums; ++f) tot[f] = l == 0 ? acc[f] : tot[f] + acc[f];
         }
-        sim3_unpack(tot, H, b, chi);
+        lm_unpack<7>(tot, H, b, chi);
     }
 
     double errors(const Sim3 &S) {
@@ -43,6 +44,8 @@ struct HostExec {
         }
         return tot;
     }
+
+    void update(Sim3 &S, const double *x) { sim3_update(S, x, pr.fix_scale); }
 
     int classify(int mark) {
         int bad = 0;
@@ -89,7 +92,7 @@ int sim3_host_optimize(const orbx_sim3 *S12, const orbx_sim3_camera *cam1, const
         chi2_21[i] = 0;
     }
     Sim3 out;
-    sim3_optimize(ex, load(S12), n, fix_scale, out, *n_inliers, iterations);
+    sim3_optimize(ex, load(S12), n, out, *n_inliers, iterations);
     std::memcpy(S12_out, &out, sizeof(out));
     return 0;
 }
@@ -113,7 +116,7 @@ int sim3_host_step(const orbx_sim3 *S12, const orbx_sim3_camera *cam1, const orb
     ex.flags = nullptr;
     ex.build(load(S12), H_out, b_out, chi2_out);
     double x[7];
-    const bool ok = sim3_solve(H_out, b_out, lambda, x);
+    const bool ok = lm_solve<7>(H_out, b_out, lambda, x);
     for (int j = 0; j < 7; ++j) x_out[j] = ok ? x[j] : 0.0;
     *solved = ok;
     return 0;
