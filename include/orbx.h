@@ -753,6 +753,58 @@ int orbx_sim3_debug_step(int device, const orbx_sim3 *S12, const orbx_sim3_camer
 int orbx_sim3_debug_update(int device, const orbx_sim3 *S, const double *x, int count, int fix_scale,
                            orbx_sim3 *S_out);
 
+/* ---- Sim3Solver (Sim3Solver.cc:37-423) ----------------------------------------
+ * Every RANSAC hypothesis of every solver in one launch (k_sim3_ransac): a
+ * hypothesis is Horn's closed form on three correspondences followed by the
+ * reprojection test of all n in both images; DESIGN.md §3.15 is the numeric
+ * specification.  iterate() is then a walk over stored results
+ * (OrbxSim3Solver, orbx_orbslam2.hpp). */
+typedef struct orbx_ransac_corr {  /* 32 bytes, mvnIndices1's order */
+    float X1c[3];                  /* Rcw1 * X3D1w + tcw1 (:95) */
+    float X2c[3];                  /* Rcw2 * X3D2w + tcw2 (:98) */
+    float max_err1, max_err2;      /* (float)(size_t)(9.210 * sigmaSquare): mvnMaxError1/2 hold size_t */
+} orbx_ransac_corr;
+
+typedef struct orbx_ransac_hyp {  /* 56 bytes */
+    float R[9];                   /* mR12i, row-major */
+    float t[3];                   /* mt12i */
+    float s;                      /* ms12i (exactly 1.0f with fix_scale) */
+    int32_t n_inliers;            /* mnInliersi */
+} orbx_ransac_hyp;
+
+/* One solver.  corr[n]; triples[h][3]: the three correspondence indices of each
+ * hypothesis; hyp[h]; mask[h][(n + 63) / 64]: bit i of a hypothesis's words =
+ * mvbInliersi[i].  ORBX_EINVAL for a triple with a repeated or out-of-range
+ * index and for n < 3 with h > 0; h = 0 and n = 0 are legal and write nothing.
+ * Host arrays, synchronous. */
+int orbx_sim3_ransac(int device, const orbx_sim3_camera *cam1, const orbx_sim3_camera *cam2, int fix_scale,
+                     const orbx_ransac_corr *corr, int n, const int32_t *triples, int h, orbx_ransac_hyp *hyp,
+                     uint64_t *mask);
+/* nproblems solvers at once, in CSR twice: problem p's correspondences are
+ * corr[corr_offsets[p] .. corr_offsets[p + 1]) and its hypotheses
+ * triples[3 * hyp_offsets[p] ..), hyp[hyp_offsets[p] ..) (both offset arrays
+ * start at 0 and ascend); its mask words start at the sum over q < p of
+ * h_q * ((n_q + 63) / 64).  One upload, one launch, one download; synchronous. */
+int orbx_sim3_ransac_batch(int device, const orbx_sim3_camera *cam1, const orbx_sim3_camera *cam2,
+                           const int32_t *fix_scale, const orbx_ransac_corr *corr, const int32_t *corr_offsets,
+                           const int32_t *triples, const int32_t *hyp_offsets, int nproblems, orbx_ransac_hyp *hyp,
+                           uint64_t *mask);
+/* The same on device arrays of the current device, enqueued on `stream` with
+ * no synchronisation.  d_mask_offsets[nproblems + 1]: each problem's first mask
+ * word (the sums above); max_hyp: the largest hypothesis count of a problem.
+ * The triples are not validated here: a hypothesis whose triple has a repeated
+ * or out-of-range index gets NaN R, t, s and 0 inliers, and reads nothing out
+ * of bounds.  The kernel reads nothing it did not write in this launch besides
+ * the inputs, so buffers can be reused across calls. */
+int orbx_sim3_ransac_batch_device(const orbx_sim3_camera *d_cam1, const orbx_sim3_camera *d_cam2,
+                                  const int32_t *d_fix_scale, const orbx_ransac_corr *d_corr,
+                                  const int32_t *d_corr_offsets, const int32_t *d_triples,
+                                  const int32_t *d_hyp_offsets, const int64_t *d_mask_offsets, int nproblems,
+                                  int max_hyp, orbx_ransac_hyp *d_hyp, uint64_t *d_mask, void *stream);
+/* atan2(y[k], x[k]) in double on the device for count arguments (test hook:
+ * §3.15's angle is the first use of the library's atan2 on this path). */
+int orbx_sim3_ransac_debug_atan2(int device, const double *y, const double *x, int count, double *out);
+
 /* Device evaluation of the restated sincosf / fastAtan2 (test hook). */
 int orbx_debug_trig(int device, const float *angles, float *s, float *c, int n,
                     const float *ys, const float *xs, float *atan_deg, int m);

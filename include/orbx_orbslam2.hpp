@@ -14,6 +14,8 @@
 
 #include <algorithm>
 #include <cassert>
+#include <climits>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -535,6 +537,159 @@ private:
         return orbx_vocab_load(orbx_detail::device_index(), filename.c_str(), format, &v_) == ORBX_OK;
     }
     orbx_vocab *v_ = nullptr;
+};
+
+// Sim3Solver's RANSAC state (Sim3Solver.cc:114-213) over hypotheses computed
+// on the device.  The owner (integration/Sim3Solver_orbx.cc) fills cam1, cam2,
+// fix_scale, corr, indices1 and mN1 as the reference's constructor collects
+// them; Draw takes all mRansacMaxIts index triples from the caller's
+// RandomInt with the reference's swap-with-last removal (:163-177); Prepare
+// launches the drawn hypotheses of several solvers in one
+// orbx_sim3_ransac_batch call; Iterate is iterate() with ComputeSim3 and
+// CheckInliers replaced by a lookup, and does no arithmetic.
+class OrbxSim3Solver {
+public:
+    orbx_sim3_camera cam1{}, cam2{};
+    bool fix_scale = true;
+    std::vector<orbx_ransac_corr> corr;   // mvnIndices1's order
+    std::vector<size_t> indices1;         // mvnIndices1
+    int mN1 = 0;
+
+    // SetRansacParameters (:114-138) as it is: the float epsilon, the
+    // N == minInliers case, max(1, min(., .)).  Hypotheses launched for an
+    // earlier setting are dropped.
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+        mRansacProb = probability;
+        mRansacMinInliers = minInliers;
+        mRansacMaxIts = maxIterations;
+        N = (int)corr.size();
+        float epsilon = (float)mRansacMinInliers / N;
+        int nIterations;
+        if (mRansacMinInliers == N)
+            nIterations = 1;
+        else {
+            // (a NaN or out-of-range double converts to INT_MIN on x86-64, which is what the reference gets)
+            const double v = std::ceil(std::log(1 - mRansacProb) / std::log(1 - std::pow(epsilon, 3)));
+            nIterations = v >= -2147483648.0 && v < 2147483648.0 ? (int)v : INT_MIN;
+        }
+        mRansacMaxIts = std::max(1, std::min(nIterations, mRansacMaxIts));
+        mnIterations = 0;
+        triples.clear();
+        hyp.clear();
+        mask.clear();
+        drawn = launched = false;
+    }
+
+    // All mRansacMaxIts triples (none where iterate() returns at once)
+    template <typename RandomInt>
+    void Draw(RandomInt &&randomInt) {
+        triples.clear();
+        drawn = true;
+        launched = false;
+        if (N < mRansacMinInliers || N < 3) return;
+        std::vector<int32_t> avail;
+        triples.reserve(3 * (size_t)mRansacMaxIts);
+        for (int it = 0; it < mRansacMaxIts; ++it) {
+            avail.resize(N);
+            for (int i = 0; i < N; ++i) avail[i] = i;
+            for (short i = 0; i < 3; ++i) {
+                const int randi = randomInt(0, (int)avail.size() - 1);
+                triples.push_back(avail[randi]);
+                avail[randi] = avail.back();
+                avail.pop_back();
+            }
+        }
+    }
+
+    bool Drawn() const { return drawn; }
+    bool Launched() const { return launched; }
+
+    // One launch for every solver of the list that is drawn and not launched
+    static void Prepare(const std::vector<OrbxSim3Solver *> &solvers) {
+        std::vector<OrbxSim3Solver *> todo;
+        for (OrbxSim3Solver *s : solvers) {
+            if (!s || !s->drawn || s->launched) continue;
+            if (s->triples.empty())
+                s->launched = true;   // below the minimum: iterate() returns at once
+            else
+                todo.push_back(s);
+        }
+        if (todo.empty()) return;
+        const size_t P = todo.size();
+        std::vector<orbx_sim3_camera> c1(P), c2(P);
+        std::vector<int32_t> fix(P), co(P + 1, 0), ho(P + 1, 0), tri;
+        std::vector<orbx_ransac_corr> K;
+        std::vector<size_t> mo(P + 1, 0);
+        for (size_t p = 0; p < P; ++p) {
+            const OrbxSim3Solver &s = *todo[p];
+            c1[p] = s.cam1;
+            c2[p] = s.cam2;
+            fix[p] = s.fix_scale ? 1 : 0;
+            K.insert(K.end(), s.corr.begin(), s.corr.end());
+            tri.insert(tri.end(), s.triples.begin(), s.triples.end());
+            co[p + 1] = (int32_t)K.size();
+            ho[p + 1] = (int32_t)(tri.size() / 3);
+            mo[p + 1] = mo[p] + (s.triples.size() / 3) * s.Words();
+        }
+        std::vector<orbx_ransac_hyp> H(tri.size() / 3 + 1);
+        std::vector<uint64_t> M(mo[P] + 1);
+        orbx_detail::check(orbx_sim3_ransac_batch(orbx_detail::device_index(), c1.data(), c2.data(), fix.data(),
+                                                  K.data(), co.data(), tri.data(), ho.data(), (int)P, H.data(),
+                                                  M.data()),
+                           "Sim3Solver");
+        for (size_t p = 0; p < P; ++p) {
+            OrbxSim3Solver &s = *todo[p];
+            s.hyp.assign(H.begin() + ho[p], H.begin() + ho[p + 1]);
+            s.mask.assign(M.begin() + mo[p], M.begin() + mo[p + 1]);
+            s.launched = true;
+        }
+    }
+
+    // iterate() (:140-207).  Returns the index of the hypothesis it returns, or -1.
+    int Iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers) {
+        bNoMore = false;
+        vbInliers = std::vector<bool>(mN1, false);
+        nInliers = 0;
+        if (N < mRansacMinInliers) {
+            bNoMore = true;
+            return -1;
+        }
+        int nCurrentIterations = 0;
+        while (mnIterations < mRansacMaxIts && nCurrentIterations < nIterations) {
+            nCurrentIterations++;
+            const int k = mnIterations++;
+            const int mnInliersi = hyp[k].n_inliers;
+            if (mnInliersi >= mnBestInliers) {
+                mnBestInliers = mnInliersi;
+                best = k;
+                if (mnInliersi > mRansacMinInliers) {
+                    nInliers = mnInliersi;
+                    const uint64_t *w = &mask[(size_t)k * Words()];
+                    for (int i = 0; i < N; i++)
+                        if ((w[i >> 6] >> (i & 63)) & 1) vbInliers[indices1[i]] = true;
+                    return k;
+                }
+            }
+        }
+        if (mnIterations >= mRansacMaxIts) bNoMore = true;
+        return -1;
+    }
+
+    int MaxIterations() const { return mRansacMaxIts; }
+    int Correspondences() const { return N; }
+    const orbx_ransac_hyp *Best() const { return best < 0 ? nullptr : &hyp[best]; }
+    const orbx_ransac_hyp &Hypothesis(int k) const { return hyp[k]; }
+
+private:
+    size_t Words() const { return ((size_t)N + 63) / 64; }
+    int N = 0;
+    double mRansacProb = 0.99;
+    int mRansacMinInliers = 6, mRansacMaxIts = 300;
+    int mnIterations = 0, mnBestInliers = 0, best = -1;
+    bool drawn = false, launched = false;
+    std::vector<int32_t> triples;
+    std::vector<orbx_ransac_hyp> hyp;
+    std::vector<uint64_t> mask;
 };
 
 }  // namespace ORB_SLAM2

@@ -16,9 +16,10 @@ from .frame_aux import compute_distinctive_descriptors, cvt_gray, undistort_keyp
 from .keyframe_db import KeyFrameDatabase  # noqa: F401
 from .optimizer import local_bundle_adjustment, pose_optimization, pose_optimization_batch  # noqa: F401
 from .optimizer import optimize_sim3, optimize_sim3_batch  # noqa: F401
+from .sim3solver import Sim3Solver, sim3_ransac, sim3_ransac_batch  # noqa: F401
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "load", "ORBextractor", "ORBmatcher", "Frame",
            "compute_stereo_matches", "stereo_from_rgbd", "ORBVocabulary",
            "compute_distinctive_descriptors", "cvt_gray", "undistort_keypoints", "KeyFrameDatabase",
            "local_bundle_adjustment", "pose_optimization", "pose_optimization_batch", "optimize_sim3",
-           "optimize_sim3_batch"]
+           "optimize_sim3_batch", "Sim3Solver", "sim3_ransac", "sim3_ransac_batch"]

@@ -159,6 +159,10 @@ _SIGNATURES = {
     "orbx_optimize_sim3_batch_device": (I32, [P, P, P, P, P, I32, P, P, P, P, P, P, P, P, P]),
     "orbx_sim3_debug_step": (I32, [I32, P, P, P, P, I32, F32, I32, P, I32, ctypes.c_double, P, P, P, P, P]),
     "orbx_sim3_debug_update": (I32, [I32, P, P, I32, I32, P]),
+    "orbx_sim3_ransac": (I32, [I32, P, P, I32, P, I32, P, I32, P, P]),
+    "orbx_sim3_ransac_batch": (I32, [I32, P, P, P, P, P, P, P, I32, P, P]),
+    "orbx_sim3_ransac_batch_device": (I32, [P, P, P, P, P, P, P, P, I32, I32, P, P, P]),
+    "orbx_sim3_ransac_debug_atan2": (I32, [I32, P, P, I32, P]),
 }
 
 # orbx_covis_fn
