@@ -805,6 +805,66 @@ int orbx_sim3_ransac_batch_device(const orbx_sim3_camera *d_cam1, const orbx_sim
  * §3.15's angle is the first use of the library's atan2 on this path). */
 int orbx_sim3_ransac_debug_atan2(int device, const double *y, const double *x, int count, double *out);
 
+/* ---- CreateNewMapPoints' triangulation (LocalMapping.cc:334-480) ---------------
+ * Every matched pair of every neighbour of a keyframe in one launch
+ * (k_triangulate): the ray parallax test, the linear triangulation or the stereo
+ * unprojection, the two depth tests, the two reprojection tests and the
+ * scale-consistency test; DESIGN.md §3.16 is the numeric specification.  A
+ * pair's result depends on no map state; the order-dependent rest of the loop
+ * (CheckNewKeyFrames, a feature that already got its point, new MapPoint) is a
+ * host walk over the stored results. */
+typedef struct orbx_tri_view {  /* 96 bytes: one keyframe as the loop reads it */
+    float Tcw[12];              /* [Rcw | tcw], rows of four */
+    float Ow[3];                /* GetCameraCenter() */
+    float fx, fy, cx, cy, invfx, invfy, mbf, mb;
+    float pad;
+} orbx_tri_view;
+
+typedef struct orbx_tri_obs {  /* 32 bytes */
+    float u, v;                /* mvKeysUn[idx].pt */
+    float ur, depth;           /* mvuRight[idx] (< 0: monocular), mvDepth[idx] */
+    float raw_u, raw_v;        /* mvKeys[idx].pt, read by UnprojectStereo */
+    float sigma2, scale;       /* mvLevelSigma2[octave], mvScaleFactors[octave] */
+} orbx_tri_obs;
+
+typedef struct orbx_tri_pair {  /* 64 bytes */
+    orbx_tri_obs o1, o2;        /* the current keyframe's feature, the neighbour's */
+} orbx_tri_pair;
+
+/* status: 0 created; 1 no stereo and low parallax (:397); 2 w == 0 (:381);
+ * 3 z1 <= 0; 4 z2 <= 0; 5 reprojection in keyframe 1; 6 in keyframe 2; 7 zero
+ * distance (:470); 8 scale ratio (:478); 9 (the _device entry only) an
+ * observation with ur >= 0 and no positive depth.  X: the point where it was
+ * computed (status 0 and 3..8), zero otherwise. */
+typedef struct orbx_tri_point {  /* 16 bytes */
+    float X[3];
+    int32_t status;
+} orbx_tri_point;
+
+/* One neighbour.  v1: the current keyframe, v2: the neighbour; ratio_factor:
+ * 1.5f * mfScaleFactor; pairs[n], out[n].  ORBX_EINVAL for n < 0 and for an
+ * observation with ur >= 0 whose depth is not positive (the reference
+ * dereferences an empty Mat there); n = 0 is legal and writes nothing.  Host
+ * arrays, synchronous. */
+int orbx_triangulate(int device, const orbx_tri_view *v1, const orbx_tri_view *v2, float ratio_factor,
+                     const orbx_tri_pair *pairs, int n, orbx_tri_point *out);
+/* nproblems neighbours (of one keyframe or of many) at once, in CSR: problem
+ * p's pairs are pairs[offsets[p] .. offsets[p + 1]), its views v1[p], v2[p] and
+ * its factor ratio_factor[p]; offsets start at 0 and ascend (else ORBX_EINVAL).
+ * One upload, one launch, one download; synchronous. */
+int orbx_triangulate_batch(int device, const orbx_tri_view *v1, const orbx_tri_view *v2, const float *ratio_factor,
+                           const orbx_tri_pair *pairs, const int32_t *offsets, int nproblems, orbx_tri_point *out);
+/* The same on device arrays of the current device, enqueued on `stream` with
+ * no synchronisation.  total_pairs: offsets[nproblems].  Only the arguments
+ * themselves are checked (ORBX_EINVAL for a negative count or a null pointer
+ * with work to do); no array is read on the host, so the offsets and the
+ * observations are not validated: a pair with the invalid stereo depth gets
+ * status 9 and a zero X, the others are unaffected.  The kernel reads nothing it did not write in this
+ * launch besides the inputs, so buffers can be reused across calls. */
+int orbx_triangulate_batch_device(const orbx_tri_view *d_v1, const orbx_tri_view *d_v2, const float *d_ratio_factor,
+                                  const orbx_tri_pair *d_pairs, const int32_t *d_offsets, int nproblems,
+                                  int total_pairs, orbx_tri_point *d_out, void *stream);
+
 /* Device evaluation of the restated sincosf / fastAtan2 (test hook). */
 int orbx_debug_trig(int device, const float *angles, float *s, float *c, int n,
                     const float *ys, const float *xs, float *atan_deg, int m);

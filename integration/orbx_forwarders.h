@@ -165,4 +165,14 @@ std::vector<std::vector<std::pair<size_t, size_t>>> OrbxSearchForTriangulationBa
     KeyFrame *pKF1, const std::vector<KeyFrame *> &vpNeighKFs, const std::vector<cv::Mat> &vF12, bool bOnlyStereo,
     float nnratio = 0.6f);
 
+// LocalMapping::CreateNewMapPoints (LocalMapping.cc:334-480): the loop body
+// that consumes vPairs[i] (OrbxSearchForTriangulationBatch's result) for every
+// neighbour as one device batch (LocalMapping_triangulate_orbx.cc, DESIGN.md
+// §3.16).  Returns per neighbour, in pair order, the point and why it was or
+// was not kept (orbx_tri_point::status, 0 = create it).  The walk over the
+// results stays with the caller.
+std::vector<std::vector<orbx_tri_point>> OrbxTriangulateBatch(
+    KeyFrame *pKF1, const std::vector<KeyFrame *> &vpNeighKFs,
+    const std::vector<std::vector<std::pair<size_t, size_t>>> &vPairs);
+
 }  // namespace ORB_SLAM2

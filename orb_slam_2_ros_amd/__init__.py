@@ -17,9 +17,11 @@ from .keyframe_db import KeyFrameDatabase  # noqa: F401
 from .optimizer import local_bundle_adjustment, pose_optimization, pose_optimization_batch  # noqa: F401
 from .optimizer import optimize_sim3, optimize_sim3_batch  # noqa: F401
 from .sim3solver import Sim3Solver, sim3_ransac, sim3_ransac_batch  # noqa: F401
+from .triangulate import create_new_map_points_walk, triangulate, triangulate_batch  # noqa: F401
 
 __all__ = ["KEYPOINT_DTYPE", "OrbxError", "load", "ORBextractor", "ORBmatcher", "Frame",
            "compute_stereo_matches", "stereo_from_rgbd", "ORBVocabulary",
            "compute_distinctive_descriptors", "cvt_gray", "undistort_keypoints", "KeyFrameDatabase",
            "local_bundle_adjustment", "pose_optimization", "pose_optimization_batch", "optimize_sim3",
-           "optimize_sim3_batch", "Sim3Solver", "sim3_ransac", "sim3_ransac_batch"]
+           "optimize_sim3_batch", "Sim3Solver", "sim3_ransac", "sim3_ransac_batch", "triangulate",
+           "triangulate_batch", "create_new_map_points_walk"]

@@ -163,6 +163,9 @@ _SIGNATURES = {
     "orbx_sim3_ransac_batch": (I32, [I32, P, P, P, P, P, P, P, I32, P, P]),
     "orbx_sim3_ransac_batch_device": (I32, [P, P, P, P, P, P, P, P, I32, I32, P, P, P]),
     "orbx_sim3_ransac_debug_atan2": (I32, [I32, P, P, I32, P]),
+    "orbx_triangulate": (I32, [I32, P, P, F32, P, I32, P]),
+    "orbx_triangulate_batch": (I32, [I32, P, P, P, P, P, I32, P]),
+    "orbx_triangulate_batch_device": (I32, [P, P, P, P, P, I32, I32, P, P]),
 }
 
 # orbx_covis_fn
